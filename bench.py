@@ -2,9 +2,13 @@
 """bench.py -- throughput of the MI355X-native Strelka2 hot path on the germline chr20-style synthetic workload
 (BASELINE.json configs[1]): 150 bp reads x 64 candidate alignments (hot path A) and 40x pileup loci (hot path B).
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up and times the headline leg (a5, below) and prints one JSON line; --dump-outputs DIR also writes what
+its last timed step computed (dump_a5_outputs).  --full adds every other leg: sum_only, hot path B, pileup, somatic, indel, feed,
+whole-read, the end-to-end legs against the reference, the CPU baseline and the roofline objects.
 
 One process per GPU.  The path shards by independent genome segments, so every rank scores its own,
 equally sized batch ("weak" scaling) and there is NO data-path collective; torch.distributed is used only for the
@@ -33,6 +37,12 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICRO
 A_BYTES_PER_READ = 2 * 150 + 64 * (160 + 8)  # 11 052 B per 9 600 cells
 B_BYTES_PER_CALL_DE = 6                      # sk_dependent_eprob: 2 B call in + 4 B de out
 B_BYTES_PER_LOCUS_FIXED = 1 + 120            # ref base + results
+
+METRIC = ("candidate-alignment scoring cells/s (read bases x candidate alignments; Strelka2 has no pair-HMM, "
+          "SURVEY.md section 0) + germline loci/s + 40x WGS-like germline wall-clock (e2e) + 110x/40x somatic wall-clock (e2e_somatic)")
+A5_WORKLOAD = ("scoreCandidateAlignment as one function -- per GPU per step %d reads of 150 bp x %.1f candidate alignments each (5-7 "
+               "candidate indels around them), from the candidate alignments the device search left (PCal) to one double each: one "
+               "kernel (F5: the walk of each alignment's path + the terms of its bases, penalties and clips).")
 
 
 def parse():
@@ -79,7 +89,22 @@ def parse():
     ap.add_argument("--cpu-reads", type=int, default=1500, help="reads in the CPU-baseline sample (x64 candidates)")
     ap.add_argument("--cpu-loci", type=int, default=2000000, help="loci in the CPU-baseline sample")
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="CPU time spent on the alignment-scoring sample")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg besides the headline: sum_only, loci, pileup, somatic, indel, global-align, feed and whole-read legs, "
+                         "the end-to-end legs against the reference, the CPU baseline and the roofline objects (without it a run sets up, "
+                         "warms up and times the headline leg alone)")
+    ap.add_argument("--leg-steps", type=int, default=20,
+                    help="--full: timed steps of every leg besides the headline, at most --steps (a quarter of them for the feed, "
+                         "pileup-stream and whole-read legs); the headline always times --steps")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the headline's last step computed as DIR/<name>.npy (see dump_a5_outputs)")
     return ap.parse_args()
+
+
+def side_leg_steps(args):
+    """timed steps of the --full legs besides the headline: --steps, at most --leg-steps (a --steps sized for the ~1 ms headline
+    would otherwise run the 60 ms .. 400 ms steps of the other legs as many times)"""
+    return max(1, min(args.steps, args.leg_steps))
 
 
 def cpu_baseline(args):
@@ -438,7 +463,7 @@ def realign_processes_leg(args, n_procs):
     sync = tempfile.mkdtemp(prefix="sk_bench_sync_")
     try:
         env = dict(os.environ, SK_BENCH_SYNC_DIR=sync)
-        steps = max(3, args.steps // 4)
+        steps = max(3, side_leg_steps(args) // 4)
         procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__), "--only", "realign", "--steps", str(steps), "--realign-reads", str(args.realign_reads)],
                                   stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env) for _ in range(n_procs)]
         for name in ("sparse", "dense"):
@@ -527,6 +552,33 @@ def a5_leg(args, capi, synth):
     return step, meta, event_ms
 
 
+def dump_a5_outputs(capi, meta, out_dir):
+    """--dump-outputs: the a5 job's results as its caller receives them (sk_realign_job_read_result), read after the timed steps, as
+    float64 arrays under DIR: per read a5_n_candidate_alignments, a5_max_score (the score of its best candidate alignment),
+    a5_is_realigned, a5_realign_pos and a5_n_indel_scores; per (read, indel) score in read order a5_ref_lnp and a5_indel_lnp.  The timed
+    step relaunches the job's own scoring launch (F5) over the same records; for a job of this size the library keeps those scores on
+    the device and hands them on only through these results.  The inputs are seeded (a5_leg), so two builds run with the same arguments
+    can be compared output for output."""
+    job = meta["_keep"][0]
+    L = capi.lib()
+    n = job.n_reads()
+    per_read = np.zeros((5, n))
+    ref_lnp, indel_lnp = [], []
+    r = capi.ReadResult()
+    for i in range(n):
+        if L.sk_realign_job_read_result(job._j, i, C.byref(r)):
+            raise RuntimeError("--dump-outputs: no result for read %d of the a5 job" % i)
+        per_read[:, i] = (r.n_candidate_alignments, r.max_score, r.is_realigned, r.realign_pos, r.n_scores)
+        for q in range(r.n_scores):
+            ref_lnp.append(r.scores[q].ref_lnp)
+            indel_lnp.append(r.scores[q].indel_lnp)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in zip(("n_candidate_alignments", "max_score", "is_realigned", "realign_pos", "n_indel_scores"), per_read):
+        np.save(os.path.join(out_dir, "a5_%s.npy" % name), a)
+    np.save(os.path.join(out_dir, "a5_ref_lnp.npy"), np.array(ref_lnp, np.float64))
+    np.save(os.path.join(out_dir, "a5_indel_lnp.npy"), np.array(indel_lnp, np.float64))
+
+
 def pmc_traffic(args):
     """HBM bytes per launch from the newest committed PMC summary (profiles/*_pmc_traffic.json: separate rocprofv3 --pmc
     FETCH_SIZE / WRITE_SIZE passes over this same command, tools/gpu_round.sh) -- used only when that run had the same
@@ -565,9 +617,9 @@ def main():
     # ---- end to end FIRST when this is the only rank: the caller processes of these legs share the GPU eight at a time, and eight is
     # all the device runs side by side -- a ninth process with a queue on it (this one, once it has initialised HIP) puts all of them
     # under the driver's time-slicing (1.46x instead of 1.6x on the germline leg, profiles/r03_v20_bench.json vs r03_v19).  So the
-    # legs run before this process creates its context.
+    # legs run before this process creates its context.  (They are --full legs: a plain run times the headline alone.)
     e2e = e2e_somatic = e2e_box = e2e_somatic_box = None
-    if world == 1 and (not args.only or args.only.startswith("e2e")):
+    if world == 1 and ((args.full and not args.only) or args.only.startswith("e2e")):
         if args.e2e_bp > 0 and args.only in ("", "e2e", "e2e_germline"):
             e2e = e2e_leg(args, 0, 1, local_rank, lambda: None, lambda v: v, with_reference=not args.no_cpu_baseline)
         if args.e2e_somatic_bp > 0 and args.only in ("", "e2e", "e2e_somatic"):
@@ -579,7 +631,7 @@ def main():
             if args.e2e_somatic_bp > 0 and args.only in ("", "e2e", "e2e_box", "e2e_somatic_box"):
                 e2e_somatic_box = e2e_box_leg(args, local_rank, mode="somatic")
     realign_processes = None
-    if world == 1 and not args.only and args.realign_processes > 0:
+    if world == 1 and args.full and not args.only and args.realign_processes > 0:
         from strelka_amd import farm as _farm
         realign_processes = realign_processes_leg(args, max(1, min(args.realign_processes, len(_farm.usable_cores()), args.e2e_max_procs_per_gpu)))
     e2e_legs = {"e2e": e2e, "e2e_somatic": e2e_somatic, "e2e_box": e2e_box, "e2e_somatic_box": e2e_somatic_box}
@@ -725,6 +777,42 @@ def main():
         print(json.dumps({"only": "feed_slice", "kernels": res}))
         return
 
+    region = shard.Region(dist, world, torch.cuda.synchronize,
+                          lambda v: torch.tensor(v, dtype=torch.float64, device=dev))
+
+    def timed(fn, steps, warmup, units_per_step):
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
+        dt, units = region.timed(fn, steps, warmup, units_per_step,
+                                 on_step=lambda i, before: evs[i][0 if before else 1].record())
+        kern_ms = float(np.mean([s.elapsed_time(e) for s, e in evs]))
+        return dt, units, kern_ms
+
+    if not args.full:
+        # ---- a plain run: the headline leg alone (a5 below), its outputs if asked, and the result line ----
+        a5_step, a5_meta, a5_event_ms = a5_leg(args, capi, synth)
+        dt_a5, a5_cells, _ = timed(a5_step, args.steps, args.warmup, a5_meta["cells"])
+        kms_a5 = float(np.mean(a5_event_ms[-args.steps:]))
+        if args.dump_outputs and rank == 0:
+            dump_a5_outputs(capi, a5_meta, args.dump_outputs)
+        a5_meta.pop("_keep")
+        if rank == 0:
+            print(json.dumps({
+                "metric": METRIC, "value": a5_cells / dt_a5, "unit": "cells/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                "ms_per_step": dt_a5 / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+                "dtype": "f64", "data": "synthetic",
+                "config": {"workload": "germline chr20-style synthetic (BASELINE.json configs[1]).  Headline: " + A5_WORKLOAD
+                                       % (a5_meta["reads"], a5_meta["candidate_alignments_per_read"]) + "  The other legs: --full",
+                           "reads_per_step_per_gpu": a5_meta["reads"], "candidates_per_read": a5_meta["candidate_alignments_per_read"],
+                           "read_len": 150, "sharding": "independent segments per GPU, no collective"},
+                "a5": dict(a5_meta, kernel_ms=kms_a5)}), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    leg_steps = side_leg_steps(args)
+    leg_warmup = min(args.warmup, leg_steps)
+
     # ---- resident inputs (per rank: an independent batch, seeded by rank = an independent genome segment) ----
     rng = np.random.default_rng(1000 + rank)
     ua = min(args.unique_reads, args.reads)
@@ -738,19 +826,9 @@ def main():
     gopt = capi.germline_options()
     torch.cuda.synchronize()
 
-    region = shard.Region(dist, world, torch.cuda.synchronize,
-                          lambda v: torch.tensor(v, dtype=torch.float64, device=dev))
-
-    def timed(fn, steps, warmup, units_per_step):
-        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
-        dt, units = region.timed(fn, steps, warmup, units_per_step,
-                                 on_step=lambda i, before: evs[i][0 if before else 1].record())
-        kern_ms = float(np.mean([s.elapsed_time(e) for s, e in evs]))
-        return dt, units, kern_ms
-
     # ---- hot path A ----
     cells_per_step = int(np.diff(ha.read_off).astype(np.int64).dot(np.diff(ha.cal_off).astype(np.int64))) * tile_a
-    dt_a, cells, kms_a = timed(lambda: da.score(), args.steps, args.warmup, cells_per_step)
+    dt_a, cells, kms_a = timed(lambda: da.score(), leg_steps, leg_warmup, cells_per_step)
     value = cells / dt_a
     alg_bytes_a = A_BYTES_PER_READ * da.n_reads
     ach_a = alg_bytes_a / (kms_a * 1e-3) / 1e9
@@ -759,12 +837,14 @@ def main():
     a5_step, a5_meta, a5_event_ms = a5_leg(args, capi, synth)
     dt_a5, a5_cells, _ = timed(a5_step, args.steps, args.warmup, a5_meta["cells"])
     kms_a5 = float(np.mean(a5_event_ms[-args.steps:]))
+    if args.dump_outputs and rank == 0:  # (before the legs below run device jobs of their own)
+        dump_a5_outputs(capi, a5_meta, args.dump_outputs)
     a5_keep = a5_meta.pop("_keep")
 
     # ---- hot path B (germline): dependent eprob + site genotype call ----
     def step_b():
         db.site_digt_call_fused(gopt)
-    dt_b, loci, kms_b = timed(step_b, args.steps, args.warmup, db.n_loci)
+    dt_b, loci, kms_b = timed(step_b, leg_steps, leg_warmup, db.n_loci)
     loci_per_s = loci / dt_b
     alg_bytes_b = 6 * db.n_calls + B_BYTES_PER_LOCUS_FIXED * db.n_loci
     ach_b = alg_bytes_b / (kms_b * 1e-3) / 1e9
@@ -772,7 +852,7 @@ def main():
     # ---- row a8: reads -> pileup columns (feeds hot path B) ----
     rbatch, rb_loci = synth.pileup_reads_flat(args.pileup_reads, rng)
     dr = device.DeviceReadBatch(rbatch, rb_loci, dev)
-    dt_p, pbases, kms_p = timed(lambda: dr.pileup(), args.steps, args.warmup, rbatch.n_bases)
+    dt_p, pbases, kms_p = timed(lambda: dr.pileup(), leg_steps, leg_warmup, rbatch.n_bases)
     pileup_alg_bytes = 8 * rbatch.n_bases  # 4 B per read base (P1) + 4 B per call (P2)
     del dr
 
@@ -793,7 +873,7 @@ def main():
         stream.begin_region(sb.ref_seq, 0, 0, sb_loci + 200)
         for sub, final_to in subs:
             stream.push_raw(sub, final_to)
-    dt_ps, ps_bases, _ = timed(stream_step, max(2, args.steps // 4), 1, sb.n_bases)
+    dt_ps, ps_bases, _ = timed(stream_step, max(2, leg_steps // 4), 1, sb.n_bases)
     stream_windows = len(subs)
     stream.close()
 
@@ -802,7 +882,7 @@ def main():
     tile_s = max(1, args.somatic_loci // ns.n_loci)
     dns = device.DevicePileupBatch(ns, dev, tile=tile_s)
     dts = device.DevicePileupBatch(ts, dev, tile=tile_s)
-    dt_s, sloci, kms_s = timed(lambda: device.somatic_snv_call_dev(dns, dts), args.steps, args.warmup, dns.n_loci)
+    dt_s, sloci, kms_s = timed(lambda: device.somatic_snv_call_dev(dns, dts), leg_steps, leg_warmup, dns.n_loci)
     somatic_calls = dns.n_calls + dts.n_calls
     somatic_loci_n = dns.n_loci
     del dns, dts
@@ -813,33 +893,33 @@ def main():
     # (the library's default -- the fast form, what the drop-in runs -- is the leg's figure; the exact form beside it)
     fast_opt_i = capi.indel_options(True, exact=False)
     assert fast_opt_i.fast_form == 1
-    dt_i, iloci, kms_i = timed(lambda: drs.grid_lhood(opt=fast_opt_i), args.steps, args.warmup, drs.n_indels)
+    dt_i, iloci, kms_i = timed(lambda: drs.grid_lhood(opt=fast_opt_i), leg_steps, leg_warmup, drs.n_indels)
     dt_if, iloci_f, kms_if = dt_i, iloci, kms_i
-    dt_ix, iloci_x, kms_ix = timed(lambda: drs.grid_lhood(opt=capi.indel_options(True, exact=True)), args.steps, args.warmup, drs.n_indels)
+    dt_ix, iloci_x, kms_ix = timed(lambda: drs.grid_lhood(opt=capi.indel_options(True, exact=True)), leg_steps, leg_warmup, drs.n_indels)
     indel_alg_bytes = 16 * drs.n_reads + 8 * 21 * drs.n_indels  # 16 B per read + 8 B per state
     # ... and on the same reads with ONE read length, what a WGS sample has (the batch above mixes lengths 8..200 into 15 % of the reads, a
     # test input): the two logs of get_het_observed_allele_ratio are then 19 pairs per indel, not per read
     hrs.read_length[:] = 150
     drs1 = device.DeviceReadScoreBatch(hrs, dev)
-    dt_i1, iloci_1, kms_i1 = timed(lambda: drs1.grid_lhood(opt=capi.indel_options(True, exact=True)), args.steps, args.warmup, drs1.n_indels)
+    dt_i1, iloci_1, kms_i1 = timed(lambda: drs1.grid_lhood(opt=capi.indel_options(True, exact=True)), leg_steps, leg_warmup, drs1.n_indels)
     del drs1
     hag = synth.allele_group_batch(args.indels, rng)
     dag = device.DeviceAlleleGroupBatch(hag, dev)
-    dt_g, gloci, kms_g = timed(lambda: dag.genotype_lhoods(), args.steps, args.warmup, dag.n_groups)
+    dt_g, gloci, kms_g = timed(lambda: dag.genotype_lhoods(), leg_steps, leg_warmup, dag.n_groups)
     fast_opt_g = capi.indel_options(False)
     fast_opt_g.fast_form = 1
-    dt_gf, gloci_f, kms_gf = timed(lambda: dag.genotype_lhoods(opt=fast_opt_g), args.steps, args.warmup, dag.n_groups)
+    dt_gf, gloci_f, kms_gf = timed(lambda: dag.genotype_lhoods(opt=fast_opt_g), leg_steps, leg_warmup, dag.n_groups)
     group_alg_bytes = (8 * capi.MAX_ALT + 5) * dag.n_reads + 128 * dag.n_groups
     hag.read_length[:] = 150  # ... and with one read length, as for the grid kernel
     dag1 = device.DeviceAlleleGroupBatch(hag, dev)
-    dt_g1, gloci_1, kms_g1 = timed(lambda: dag1.genotype_lhoods(), args.steps, args.warmup, dag1.n_groups)
+    dt_g1, gloci_1, kms_g1 = timed(lambda: dag1.genotype_lhoods(), leg_steps, leg_warmup, dag1.n_groups)
     del dag1
     del drs, dag
 
     # ---- next row f2: GlobalAligner<int>, haplotype vs reference segment (device-resident entry point) ----
     pairs = synth.align_pairs(args.align_problems, rng)
     dga = device.DeviceGlobalAlignBatch(pairs, dev)
-    dt_ga, ga_cells, kms_ga = timed(lambda: dga.align(), args.steps, args.warmup, dga.cells)
+    dt_ga, ga_cells, kms_ga = timed(lambda: dga.align(), leg_steps, leg_warmup, dga.cells)
     n_ga = dga.n
     ga_alg_bytes = dga.nq + dga.nr + 72 * dga.n  # sequences in, score / begin / ~8 path segments out per problem
     del dga
@@ -850,7 +930,7 @@ def main():
         bgzf_image = np.frombuffer(f.read(), np.uint8)
     n_fix_blocks = len(capi.bgzf_scan(bgzf_image)[0]) - 1
     dfeed = device.DeviceBgzfBatch(bgzf_image, dev, tile=max(1, args.feed_blocks // n_fix_blocks))
-    dt_f, feed_bytes, kms_f = timed(lambda: dfeed.inflate(), max(2, args.steps // 4), 1, dfeed.out_bytes)
+    dt_f, feed_bytes, kms_f = timed(lambda: dfeed.inflate(), max(2, leg_steps // 4), 1, dfeed.out_bytes)
     assert int(dfeed.status.abs().sum().item()) == 0, "BGZF inflation reported a malformed block"
     feed_alg_bytes = dfeed.in_bytes + dfeed.out_bytes
     feed_blocks = dfeed.n_blocks
@@ -861,7 +941,7 @@ def main():
     for kern in ("wave", "thread"):
         os.environ["SK_INFLATE_KERNEL"] = kern
         dsm = device.DeviceBgzfBatch(bgzf_image, dev, tile=max(1, 512 // n_fix_blocks))
-        dt_fs, fs_bytes, kms_fs = timed(lambda: dsm.inflate(), max(2, args.steps // 4), 1, dsm.out_bytes)
+        dt_fs, fs_bytes, kms_fs = timed(lambda: dsm.inflate(), max(2, leg_steps // 4), 1, dsm.out_bytes)
         assert int(dsm.status.abs().sum().item()) == 0, "BGZF inflation reported a malformed block"
         feed_small[kern] = {"blocks": dsm.n_blocks, "inflated_bytes": dsm.out_bytes, "kernel_ms": kms_fs, "inflated_bytes_per_s": fs_bytes / dt_fs}
         del dsm
@@ -873,7 +953,7 @@ def main():
                      ("_dense", dict(enumeration=2, max_indels=14, reads=args.realign_reads // 6)),
                      ("_dense_host_enumeration", dict(enumeration=0, max_indels=14, reads=args.realign_reads // 6))):
         wr_step, wr_reads, wr_cals = whole_read_leg(args, capi, synth, np.random.default_rng(4242), **kw)
-        n_wr = max(2, args.steps // 4)
+        n_wr = max(2, leg_steps // 4)
         dt_wr, wr_done, _ = timed(wr_step, n_wr, 1, wr_reads)
         wr["realign%s_reads_per_s" % name] = wr_done / dt_wr
         wr["realign%s_ms_per_step" % name] = dt_wr / n_wr * 1e3
@@ -943,32 +1023,29 @@ def main():
                 o["frac"] = o["frac_measured"]
         return o
     out = {
-        "metric": "candidate-alignment scoring cells/s (read bases x candidate alignments; Strelka2 has no pair-HMM, "
-                  "SURVEY.md section 0) + germline loci/s + 40x WGS-like germline wall-clock (e2e) + 110x/40x somatic wall-clock (e2e_somatic)",
+        "metric": METRIC,
         "value": a5_cells / dt_a5, "unit": "cells/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": dt_a5 / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "germline chr20-style synthetic (BASELINE.json configs[1]).  Headline: scoreCandidateAlignment as one "
-                               "function -- per GPU per step %d reads of 150 bp x %.1f candidate alignments each (5-7 candidate indels "
-                               "around them), from the candidate alignments the device search left (PCal) to one double each: "
-                               "one kernel (F5: the walk of each alignment's path + the terms of its bases, penalties and clips).  sum_only: the table "
+        "dtype": "f64", "data": "synthetic", "leg_steps": leg_steps, "leg_warmup": leg_warmup,
+        "config": {"workload": "germline chr20-style synthetic (BASELINE.json configs[1]).  Headline: " + A5_WORKLOAD
+                               % (a5_meta["reads"], a5_meta["candidate_alignments_per_read"]) + "  sum_only: the table "
                                "sums alone over %d reads x 64 candidate alignments whose base comparisons were made before the clock "
                                "started (round 2's headline).  loci leg: %d loci, depth~Poisson(40).  e2e: see e2e.workload"
-                               % (a5_meta["reads"], a5_meta["candidate_alignments_per_read"], da.n_reads, db.n_loci),
+                               % (da.n_reads, db.n_loci),
                    "reads_per_step_per_gpu": a5_meta["reads"], "candidates_per_read": a5_meta["candidate_alignments_per_read"], "read_len": 150,
                    "loci_per_step_per_gpu": db.n_loci, "sharding": "independent segments per GPU, no collective"},
         "a5": dict(a5_meta, kernel_ms=kms_a5),
-        "sum_only_cells_per_s": value, "sum_only_ms_per_step": dt_a / args.steps * 1e3, "sum_only_reads_per_step_per_gpu": da.n_reads,
-        "pileup_read_bases_per_s": pbases / dt_p, "pileup_ms_per_step": dt_p / args.steps * 1e3,
+        "sum_only_cells_per_s": value, "sum_only_ms_per_step": dt_a / leg_steps * 1e3, "sum_only_reads_per_step_per_gpu": da.n_reads,
+        "pileup_read_bases_per_s": pbases / dt_p, "pileup_ms_per_step": dt_p / leg_steps * 1e3,
         "pileup_reads_per_step_per_gpu": rbatch.n_reads,
         "pileup_stream_read_bases_per_s": ps_bases / dt_ps, "pileup_stream_windows_per_step": stream_windows,
-        "pileup_stream_ms_per_window": dt_ps / max(2, args.steps // 4) / stream_windows * 1e3,
+        "pileup_stream_ms_per_window": dt_ps / max(2, leg_steps // 4) / stream_windows * 1e3,
         "pileup_stream_note": "sk_pileup_stream_push as the adapter calls it (site 9): windows of 2 200 reads, host buffers in, raw columns + "
                               "MAPQ tracker + genotypes of the finalised positions out, one host thread, one device round trip per window",
-        "somatic_loci_per_s": sloci / dt_s, "somatic_ms_per_step": dt_s / args.steps * 1e3,
+        "somatic_loci_per_s": sloci / dt_s, "somatic_ms_per_step": dt_s / leg_steps * 1e3,
         "somatic_loci_per_step_per_gpu": somatic_loci_n,
         "roofline_somatic": roof("somatic_classify_kernel+somatic_lhood_kernel+somatic_posterior_kernel", 2 * somatic_calls + 273 * somatic_loci_n, kms_s, som_traffic),
-        "indel_grid_loci_per_s": iloci / dt_i, "indel_grid_ms_per_step": dt_i / args.steps * 1e3,
+        "indel_grid_loci_per_s": iloci / dt_i, "indel_grid_ms_per_step": dt_i / leg_steps * 1e3,
         "roofline_indel_grid": roof("indel_grid_lhood_kernel", indel_alg_bytes, kms_i, traffic.get("indel_grid_lhood_kernel")),
         "indel_grid_fast_form_loci_per_s": iloci_f / dt_if, "indel_grid_fast_form_kernel_ms": kms_if,
         "indel_grid_exact_form_loci_per_s": iloci_x / dt_ix, "indel_grid_exact_form_kernel_ms": kms_ix,
@@ -980,7 +1057,7 @@ def main():
                           "reference's operation order to ~1e-13 relative, within north_star's 1e-5; the integer outputs are pinned by "
                           "tests/test_gpu_parity.py, the somatic end-to-end outputs stay byte-identical); *_exact_form_*: fast_form = 0, "
                           "bit-identical doubles; *_one_read_length_*: the exact form on reads of one length",
-        "allele_group_loci_per_s": gloci / dt_g, "allele_group_ms_per_step": dt_g / args.steps * 1e3,
+        "allele_group_loci_per_s": gloci / dt_g, "allele_group_ms_per_step": dt_g / leg_steps * 1e3,
         "roofline_allele_group": roof("allele_group_kernel", group_alg_bytes, kms_g, traffic.get("allele_group_kernel")),
         "roofline_pileup": roof("pileup_read_kernel+2*pileup_column_kernel_t", pileup_alg_bytes, kms_p, pil_traffic),
         "roofline_global_align": roof("global_align_kernel", ga_alg_bytes, kms_ga, traffic.get("global_align_kernel")),
@@ -990,13 +1067,13 @@ def main():
                         "(enumeration=2), *_host_enumeration = listed, flattened and finished on the host (round 1's path), *_dense = scenarios "
                         "with up to 14 indels around a read, realign_processes = the device legs driven by several caller processes at "
                         "once on the one GPU, as the reference is run for cpu_baseline (one process per core): rates summed",
-        "feed_inflated_bytes_per_s": feed_bytes / dt_f, "feed_ms_per_step": dt_f / max(2, args.steps // 4) * 1e3, "feed_bgzf_blocks_per_step": feed_blocks,
+        "feed_inflated_bytes_per_s": feed_bytes / dt_f, "feed_ms_per_step": dt_f / max(2, leg_steps // 4) * 1e3, "feed_bgzf_blocks_per_step": feed_blocks,
         "roofline_feed": roof("bgzf_inflate_kernel+bgzf_crc32_kernel", feed_alg_bytes, kms_f,
                               (traffic["bgzf_inflate_kernel"] + traffic["bgzf_crc32_kernel"]) if all(k in traffic for k in ("bgzf_inflate_kernel", "bgzf_crc32_kernel")) else None),
         "feed_slice_sized_launch": feed_small,
-        "global_align_cells_per_s": ga_cells / dt_ga, "global_align_ms_per_step": dt_ga / args.steps * 1e3,
+        "global_align_cells_per_s": ga_cells / dt_ga, "global_align_ms_per_step": dt_ga / leg_steps * 1e3,
         "global_align_problems_per_step": n_ga,
-        "loci_per_s": loci_per_s, "loci_ms_per_step": dt_b / args.steps * 1e3, "loci_dtype": "f32",
+        "loci_per_s": loci_per_s, "loci_ms_per_step": dt_b / leg_steps * 1e3, "loci_dtype": "f32",
         "roofline": roof("flatten_score_kernel (F5: flattening + scoring of a read's candidate alignments in one launch)",
                          a5_meta["algorithmic_bytes"], kms_a5, traffic.get("__a5_step__")),
         "roofline_sum_only": roof("score_wave_per_read_cols", alg_bytes_a, kms_a, traffic.get("score_wave_per_read_cols")),

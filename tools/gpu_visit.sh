@@ -31,13 +31,13 @@ for step in "$@"; do
       timeout 1800 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $OUT/pytest_gpu.log
       tail -5 $OUT/pytest_gpu.log ;;
     bench)
-      timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -c 1500 $OUT/bench.json ;;
+      timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -c 1500 $OUT/bench.json ;;
     bench_kernels)
-      timeout 600 python bench.py --no-cpu-baseline --e2e-bp 0 --e2e-somatic-bp 0 --realign-processes 0 > $OUT/bench_kernels.json 2> $OUT/bench_kernels.err; echo "bench_kernels rc=$?" ;;
+      timeout 600 python bench.py --full --no-cpu-baseline --e2e-bp 0 --e2e-somatic-bp 0 --realign-processes 0 > $OUT/bench_kernels.json 2> $OUT/bench_kernels.err; echo "bench_kernels rc=$?" ;;
     smoke)
       timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.log 2>&1; tail -1 $OUT/smoke.log ;;
     ktrace)
-      timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ktrace -o kt -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --e2e-bp 0 --e2e-somatic-bp 0 --realign-processes 0 > $OUT/ktrace.log 2>&1
+      timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ktrace -o kt -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --e2e-bp 0 --e2e-somatic-bp 0 --realign-processes 0 > $OUT/ktrace.log 2>&1
       find $OUT/ktrace -name "*kernel_stats.csv" | head -2 ;;
     ktrace_a5)  # the headline leg alone: every flatten_score_kernel launch of this trace is the full-size one (the whole bench also
                 # launches it from the realignment legs, at their jobs' sizes -- its average there is over all of them)
@@ -45,7 +45,7 @@ for step in "$@"; do
       find $OUT/ktrace_a5 -name "*kernel_stats.csv" | head -1 | xargs grep -i flatten_score | cut -c1-200 ;;
     pmc_traffic)
       for c in FETCH_SIZE WRITE_SIZE; do
-        timeout 600 rocprofv3 --pmc $c --output-format csv -d $OUT/pmc_$c -o pmc -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --e2e-bp 0 --e2e-somatic-bp 0 --realign-processes 0 > $OUT/pmc_$c.log 2>&1
+        timeout 600 rocprofv3 --pmc $c --output-format csv -d $OUT/pmc_$c -o pmc -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --e2e-bp 0 --e2e-somatic-bp 0 --realign-processes 0 > $OUT/pmc_$c.log 2>&1
         timeout 300 rocprofv3 --pmc $c --output-format csv -d $OUT/pmc_a5_$c -o pmc -- python bench.py --only a5 --steps 10 --warmup 2 > $OUT/pmc_a5_$c.log 2>&1
       done
       python tools/pmc_traffic.py $OUT > $OUT/pmc_traffic.json 2>$OUT/pmc_traffic.err; head -c 600 $OUT/pmc_traffic.json
@@ -56,7 +56,7 @@ for step in "$@"; do
       for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_WAIT_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE" \
                  "SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE"; do
         i=$((i+1))
-        timeout 600 rocprofv3 --pmc $set --output-format csv -d $OUT/pmc_sq$i -o pmc -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --e2e-bp 0 --e2e-somatic-bp 0 --realign-processes 0 > $OUT/pmc_sq$i.log 2>&1
+        timeout 600 rocprofv3 --pmc $set --output-format csv -d $OUT/pmc_sq$i -o pmc -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --e2e-bp 0 --e2e-somatic-bp 0 --realign-processes 0 > $OUT/pmc_sq$i.log 2>&1
         timeout 300 rocprofv3 --pmc $set --output-format csv -d $OUT/pmc_a5_sq$i -o pmc -- python bench.py --only a5 --steps 10 --warmup 2 > $OUT/pmc_a5_sq$i.log 2>&1
         tail -c 200 $OUT/pmc_sq$i.log
       done ;;
