@@ -831,14 +831,17 @@ struct FusedScoreArgs
 
 // a candidate alignment's slot in LDS: the walk's output -- up to F5_SEGS + 1 transitions, one per op that covers read positions and
 // one for the read's end (start position | penalties that precede the op's terms << 9 | soft clip << 15 | (pool offset - position + 256)
-// << 16) -- then the record's indel indices.  The record's header and path are in the lane's registers (F5Rec).  21 words a lane
-// instead of round 3's 39: with the table entries cut to the five words the walk reads and the rows of terms sized for the job's
-// longest read, a wave's LDS goes from 17.8 KB to under 10 KB and a CU holds 16 of them instead of 9 (profiles/r04_a5_history.txt: a
-// wave alone on a CU takes as long as nine sharing it; with sixteen the vector unit is ~85 % busy, profiles/r05_f5_history.txt).
+// << 16).  The record's header, path and indel indices are in the lane's registers (F5Rec).  17 words a lane instead of round 3's 39:
+// with the table entries cut to the five words the walk reads and the rows of terms sized for the job's longest read, a wave's LDS
+// goes from 17.8 KB to under 10 KB and a CU holds 16 of them instead of 9 (profiles/r04_a5_history.txt: a wave alone on a CU takes as
+// long as nine sharing it; with sixteen the vector unit is ~85 % busy, profiles/r05_f5_history.txt).
 constexpr int F5_SEGS = 16, F5_INDELS = 8;
-constexpr int F5_IND0 = F5_SEGS + 1, F5_SLOT = (F5_IND0 + F5_INDELS / 2) | 1; // (odd stride: conflict-free)
+constexpr int F5_SLOT = (F5_SEGS + 1) | 1; // (odd stride: conflict-free)
 __device__ __forceinline__ int f5_ent_word(const int k) { return k; }
-constexpr int F5_ROW = 2; // doubles per read position: agree, differ (a position that adds nothing reads the shared 0.0 instead)
+// doubles per read position: agree, 0.0, differ -- the read's own cases folded in (a '=' base: differ = agree; an N base and the pad
+// rows past the read: both +0.0), so that phase B only asks whether the read byte and the pool byte differ, and a position past the
+// op's end reads its row's 0.0: byte offset 0 = agree, 8 = past the op, 16 = differ
+constexpr int F5_ROW = 3;
 
 struct F5Tab // what the walk reads of a table entry
 {
@@ -851,37 +854,43 @@ struct F5Tab // what the walk reads of a table entry
 template <int MAXR>
 struct F5Lds
 {
+    // (phase B fetches a position's eight bytes as the three aligned words that hold them: up to 11 bytes past the last position;
+    // the two byte arrays first, where their words' offsets fit the immediate of a two-word LDS read)
+    uint8_t read[MAXR + 12];
+    uint8_t hap[F5_MAX_POOL + 12];
     double row[(MAXR + 8) * F5_ROW];
-    double zero; // 0.0
-    uint64_t live[9]; // entry m: 0x01 in the m low bytes (the positions of an eight-base step that belong to the op)
-    uint8_t read[MAXR + 8];
-    uint8_t hap[F5_MAX_POOL + 8];
-    uint32_t slot[64 * F5_SLOT];
+    uint32_t slot[64 * F5_SLOT]; // (phase B reads word F5_SLOT of a lane's slot too: the next lane's, or for lane 63 the table copy)
     // what the walk looks up per path segment (a chain of dependent look-ups: from HBM / L2 they cost a wave ~100 us per round)
     F5Tab tab[F5_TAB];
 };
-// (the CU hands LDS out in 1 280-byte pieces: 10 240 bytes are sixteen waves to a CU, one byte more fourteen)
+// (the CU hands LDS out in 1 280-byte pieces: 10 240 bytes are sixteen waves to a CU, one byte more fourteen; the 256-base form,
+// ~12.4 KB, still fits three four-wave blocks)
 static_assert(sizeof(F5Lds<152>) <= 10240, "sixteen waves of the short-read form to a CU");
+static_assert(3 * 4 * sizeof(F5Lds<F5_MAX_READ>) <= 160 * 1024, "three four-wave blocks of the long-read form to a CU");
+static_assert((152 + 12) % 4 == 0 && (F5_MAX_READ + 12) % 4 == 0 && (F5_MAX_POOL + 12) % 4 == 0, "the byte arrays' words stay aligned");
 static_assert(INS_CAP <= 64, "a lane an insert");
 
 // A compact record's path in the lane's registers: the walk looks at a segment's type up to a dozen times per turn (the edge
 // segments, the look-ahead for swaps, the step to the next segment) and every look from LDS is a round trip on the lane's chain.  The
 // sixteen types are 4 bits each in one 64-bit value, the sixteen lengths 16 bits each in four; segment i is a shift by i (the lengths:
-// a select among the four values first).  The indel indices stay in the slot (read once, at the walk's start).
+// a select among the four values first).  The indel indices are 6 bits each relative to the round's table copy (tab_lo: every index
+// of the round lies in [tab_lo, tab_lo + F5_TAB)), the eight of them in one 64-bit value.
 struct F5Rec
 {
     uint32_t w0, w1, w2;  // pos; lead | trail << 16; fwd | n_seg << 8 | n_indels << 16
     uint64_t types;       // segment i: bits [4i, 4i + 4)
     uint64_t l0, l1, l2, l3; // segment i: bits [16 (i & 3), + 16) of l(i >> 2)  (four values, not an array: an array indexed per lane
                           // goes to scratch memory)
-    const uint32_t* slot; // the lane's slot: indel indices at F5_IND0
+    uint64_t ind;         // indel k: bits [6k, 6k + 6), its table index - ind_lo
+    int ind_lo;
     __device__ __forceinline__ int32_t pos() const { return int32_t(w0); }
     __device__ __forceinline__ int lead() const { return int(int16_t(w1 & 0xffffu)); }
     __device__ __forceinline__ int trail() const { return int(int16_t(w1 >> 16)); }
     __device__ __forceinline__ int n_seg() const { return int((w2 >> 8) & 0xffu); }
     __device__ __forceinline__ int n_indels() const { return int((w2 >> 16) & 0xffu); }
-    __device__ __forceinline__ int indel(const int k) const { return int(int16_t((slot[F5_IND0 + (k >> 1)] >> (16 * (k & 1))) & 0xffffu)); }
+    __device__ __forceinline__ int indel(const int k) const { return ind_lo + int(unsigned(ind >> (6 * k)) & 63u); }
 };
+static_assert(F5_TAB <= 64 && 6 * F5_INDELS <= 64, "an indel index in 6 bits, eight in one value");
 
 // flatten_cal over a compact record, every look-up from the block's LDS copies: the walk of scoreCandidateAlignment :286-493 as
 // host/align_flatten.cpp states it, as ONE loop of selects.  Written with the reference's four branches (swap, sequence mismatch, insert,
@@ -1025,25 +1034,26 @@ __device__ __forceinline__ int f5_walk_selects(LDS& S, const F5Rec c, const bool
 
 // Phase B of F5, a lane its alignment, in path order (the order of score_one_generic): entering an op, the penalties that precede its
 // terms, then a soft clip's length x ln 0.25; inside an op of bases, eight positions per turn -- eight read codes against the eight pool
-// bytes they face (SWAR), each position's address: its row's agree or differ term, or the shared 0.0 (N, or past the op's end) -- eight
-// reads, eight adds.  ONE loop per lane (eight bases and the step to the next op in the same turn), so that the turns a wave makes are the
-// longest lane's, not the sum over ops of the longest op.  PLAIN: the read holds no '=' and no N (the block's lanes share the read: the
-// kernel asks once), the two tests are left out.  What is rare for a whole wave -- a penalty, a soft clip -- sits behind a vote.
-template <bool PLAIN, typename LDS>
+// bytes they face (SWAR), each position's address: its row's agree or differ term, or the row's 0.0 past the op's end (the rows already
+// hold what a '=' or an N read base adds) -- eight reads, eight adds.  ONE loop per lane (eight bases and the step to the next op in the
+// same turn), so that the turns a wave makes are the longest lane's, not the sum over ops of the longest op.  What is rare for a whole
+// wave -- a penalty, a soft clip -- sits behind a vote.
+template <typename LDS>
 __device__ __forceinline__ double f5_sum(LDS& S, const uint32_t* const myslot, const int n_ent, const double ln_noncand, const double ln_quarter)
 {
     double lnp = 0.0;
-    const unsigned zero_at = unsigned(reinterpret_cast<const unsigned char*>(&S.zero) - reinterpret_cast<const unsigned char*>(S.row));
     const unsigned char* rows = reinterpret_cast<const unsigned char*>(S.row);
     int e = 0, p = 0, stop = 0, hidx = 0;
+    // the current op's transition and the next one stay in registers: a turn reads one slot word, the one after them (word e + 1 <=
+    // n_ent <= F5_SLOT: past the read's end it is a word of the LDS object that nothing looks at)
+    uint32_t cur = myslot[f5_ent_word(0)], nxt = myslot[f5_ent_word(1)];
     // the step to the next op, by selects (the loop has one back edge); true: the read's end
     auto next_op = [&]() -> bool {
         const bool adv = (p >= stop);
-        const uint32_t cur = myslot[f5_ent_word(e)];
-        const int e1 = (e + 1 < n_ent) ? e + 1 : e;
-        const int next_start = int(myslot[f5_ent_word(e1)] & 0x1ffu);
+        const int start = int(cur & 0x1ffu), next_start = int(nxt & 0x1ffu);
         const unsigned np = adv ? ((cur >> 9) & 63u) : 0u; // (at most 4: the walk hands anything longer to the host form)
-        if (__any(np != 0u)) {
+        const bool clip = adv && (cur & (1u << 15)) != 0u; // (never the read's end: its word holds no soft clip)
+        if (__builtin_amdgcn_ballot_w64(np != 0u || clip) != 0ull) { // (both rare: one vote)
             const double l1 = __dadd_rn(lnp, ln_noncand);
             lnp = (np >= 1u) ? l1 : lnp;
             const double l2 = __dadd_rn(lnp, ln_noncand);
@@ -1052,55 +1062,58 @@ __device__ __forceinline__ double f5_sum(LDS& S, const uint32_t* const myslot, c
             lnp = (np >= 3u) ? l3 : lnp;
             const double l4 = __dadd_rn(lnp, ln_noncand);
             lnp = (np >= 4u) ? l4 : lnp;
-        }
-        if (adv && e + 1 >= n_ent) return true;
-        const int start = int(cur & 0x1ffu);
-        const bool clip = adv && (cur & (1u << 15)) != 0u;
-        if (__any(clip)) {
             const double lc = __dadd_rn(lnp, __dmul_rn(double(unsigned(next_start - start)), ln_quarter));
             lnp = clip ? lc : lnp;
         }
+        if (adv && e + 1 >= n_ent) return true;
         p = adv ? (clip ? next_start : start) : p;
         stop = adv ? next_start : stop;
         hidx = adv ? int(cur >> 16) - 256 : hidx;
-        e = adv ? e1 : e;
+        e = adv ? e + 1 : e;
+        cur = adv ? nxt : cur;
+        nxt = myslot[f5_ent_word(e + 1)];
         return false;
     };
     if (next_op()) return lnp; // (the first op: no bases before it)
     for (;;) {
         {
-            const int m = stop - p; // bases of the current op still to add (0: a soft clip just stepped over)
-            // (32-bit halves: positions 0-3, 4-7; every byte holds a 4-bit code, so a byte-wise add never carries across bytes)
-            uint32_t R[2], H[2], live[2];
-            __builtin_memcpy(R, S.read + p, 8);
-            __builtin_memcpy(H, S.hap + (p + hidx), 8);
-            __builtin_memcpy(live, &S.live[m > 8 ? 8 : m], 8);
-            constexpr uint32_t B01 = 0x01010101u, B7F = 0x7f7f7f7fu, B71 = 0x71717171u;
-            uint32_t none[2], dif8[2];
+            const int m = stop - p;          // bases of the current op still to add (0: a soft clip just stepped over)
+            const int mm = (m > 8) ? 8 : m;
+            // the eight read codes at p and the eight pool bytes they face, each from the three aligned words that hold them (a byte
+            // address read as one 8-byte word is an unaligned LDS access: replayed); 32-bit halves, positions 0-3 and 4-7
+            const int ph = p + hidx;
+            const uint32_t* const rw = reinterpret_cast<const uint32_t*>(S.read + (p & ~3));
+            const uint32_t* const hw = reinterpret_cast<const uint32_t*>(S.hap + (ph & ~3));
+            const uint32_t r0 = rw[0], r1 = rw[1], r2 = rw[2], h0 = hw[0], h1 = hw[1], h2 = hw[2];
+            const uint32_t R[2] = {__builtin_amdgcn_alignbyte(r1, r0, unsigned(p)), __builtin_amdgcn_alignbyte(r2, r1, unsigned(p))};
+            const uint32_t H[2] = {__builtin_amdgcn_alignbyte(h1, h0, unsigned(ph)), __builtin_amdgcn_alignbyte(h2, h1, unsigned(ph))};
+            // 0x18 in the bytes of the positions past the op's end (a suffix of the eight)
+            const uint64_t past = (mm >= 8) ? 0ull : (0x1818181818181818ull << (8 * mm));
+            constexpr uint32_t B0F = 0x0f0f0f0fu, B10 = 0x10101010u;
+            uint32_t sel[2]; // per byte the offset in the position's row: 0 agree, 8 past the op's end (0.0), 16 differ
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                const uint32_t ne = (((R[h] ^ H[h]) + B7F) >> 7) & B01; // 1: the bytes differ
-                if (PLAIN) {
-                    none[h] = live[h] ^ B01;
-                    dif8[h] = ne << 3;                                  // per byte: 8 = the differ term, 0 = the agree term
-                } else {
-                    const uint32_t nz = ((R[h] + B7F) >> 7) & B01;      // 1: the read base is not '='
-                    const uint32_t any = ((R[h] + B71) >> 7) & B01;     // 1: the read base is N (code 15)
-                    none[h] = any | (live[h] ^ B01);
-                    dif8[h] = (ne & nz) << 3;
-                }
+                // (the codes are 4-bit: x ^ y + 15 sets bit 4 of a byte exactly when the two differ; a byte past the op may carry into
+                // the next one, which is past the op too, and the select drops both: bit 4 from the compare where the position is the
+                // op's, bit 3 = past the op)
+                const uint32_t x = (R[h] ^ H[h]) + B0F;
+                uint32_t pm = uint32_t(past >> (32 * h));
+                // (no known bits for the compiler to act on: the select stays one three-input bit op, the bytes' extraction below the
+                // byte-select operands of the adds)
+                __asm__("" : "+v"(pm));
+                sel[h] = (B10 & ~pm & x) | (~B10 & pm);
+                __asm__("" : "+v"(sel[h]));
             }
-            const unsigned base = unsigned(8 * F5_ROW * p);
+            const unsigned base = __umul24(unsigned(8 * F5_ROW), unsigned(p));
             double v[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
-                const unsigned nb = (none[u >> 2] >> (8 * (u & 3))) & 0xffu, db = (dif8[u >> 2] >> (8 * (u & 3))) & 0xffu;
-                const unsigned at = nb ? zero_at : base + unsigned(8 * F5_ROW * u) + db;
+                const unsigned at = base + unsigned(8 * F5_ROW * u) + ((sel[u >> 2] >> (8 * (u & 3))) & 0xffu);
                 v[u] = *reinterpret_cast<const double*>(rows + at);
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u) lnp = __dadd_rn(lnp, v[u]);
-            p += (m > 8) ? 8 : m;
+            p += mm;
         }
         if (next_op()) break;
     }
@@ -1142,7 +1155,6 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
     const int n_ins = a.n_ins[r];
     int my_ins_idx = -1;    // lane k < n_ins: the table index of the read's insert k and where its sequence starts in the pool
     int32_t my_ins_off = 0;
-    bool odd_code = false;  // the read holds a '=' or an N somewhere (phase B's plain form leaves those two tests out)
     // ---- the pool's bytes (as pool_fill_kernel), the read, its rows of terms, the pool's layout
     {
         const int16_t* idx = a.ins_idx + size_t(r) * INS_CAP;
@@ -1178,9 +1190,7 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
                 if (o + i < P) S.hap[o + i] = code_of(a.ins_pool[src + uint32_t(i)]);
         }
         const SkTables* __restrict__ T = fa.tab;
-        if (lane == 0) S.zero = 0.0;
-        if (lane < 9) S.live[lane] = (lane >= 8) ? 0x0101010101010101ull : (0x0101010101010101ull & ((1ull << (8 * lane)) - 1ull));
-        for (int32_t i = lane; i < L + 8; i += 64) {
+        for (int32_t i = lane; i < L + 12; i += 64) {
             unsigned q = 0;
             uint8_t code = SK_BAM_ANY;
             if (i < L) {
@@ -1191,14 +1201,18 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
                     q = 70u;
                 }
             }
-            odd_code = odd_code || (i < L && ((code & 15u) == 0u || (code & 15u) == 15u));
             S.read[i] = code & 15u;
-            S.row[F5_ROW * i] = T->q2lncompe[q];
-            S.row[F5_ROW * i + 1] = T->q2mis[q];
+            if (i < L + 8) { // (the row of a '=' base adds its agree term either way, an N base and a pad row +0.0)
+                const unsigned c = code & 15u;
+                const bool adds = i < L && c != 15u;
+                const double agree = adds ? T->q2lncompe[q] : 0.0;
+                S.row[F5_ROW * i] = agree;
+                S.row[F5_ROW * i + 1] = 0.0;
+                S.row[F5_ROW * i + 2] = !adds ? 0.0 : (c == 0u) ? agree : T->q2mis[q];
+            }
         }
     }
     const double ln_quarter = fa.tab->ln_quarter, ln_noncand = fa.tab->ln_noncand;
-    const bool plain_codes = !__any(odd_code);
 
     // The read's candidate alignments in order of path length, longest first (a counting sort over the segment counts, the order in the
     // unused tail of the pool's bytes): a wave's walk lasts as long as its longest path, so a round of like paths wastes fewer turns
@@ -1249,14 +1263,17 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
         rec.w0 = rec.w1 = rec.w2 = 0;
         rec.types = 0;
         rec.l0 = rec.l1 = rec.l2 = rec.l3 = 0;
-        rec.slot = myslot;
+        rec.ind = 0;
+        rec.ind_lo = 0;
+        uint64_t ind_raw0 = 0, ind_raw1 = 0; // the record's eight 16-bit indel indices, until the round's table copy is placed
         if (has) {
             const PCal* src = a.pool + a.list[c0 + my_j];
             const uint4* s4 = reinterpret_cast<const uint4*>(src);
             const uint4 q0 = s4[0], q1 = s4[1], q2 = s4[2], q3 = s4[3], q4 = s4[4];
             const uint32_t* si = reinterpret_cast<const uint32_t*>(src->indels);
             const uint32_t i0 = si[0], i1 = si[1], i2 = si[2], i3 = si[3];
-            myslot[F5_IND0] = i0; myslot[F5_IND0 + 1] = i1; myslot[F5_IND0 + 2] = i2; myslot[F5_IND0 + 3] = i3;
+            ind_raw0 = uint64_t(i0) | (uint64_t(i1) << 32);
+            ind_raw1 = uint64_t(i2) | (uint64_t(i3) << 32);
             rec.w0 = q0.x;
             rec.w1 = q0.y;
             rec.w2 = q0.z;
@@ -1278,6 +1295,7 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
             fits = fits && !odd_type;
         }
         // the table entries this round's alignments name
+        auto raw_indel = [&](const int k) -> int { return int(int16_t(((k & 4) ? ind_raw1 : ind_raw0) >> (16 * (k & 3)))); };
         int tab_lo = 0;
         {
             int lo = INT_MAX, hi = INT_MIN;
@@ -1287,7 +1305,7 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
                     hi = max(hi, i);
                 };
                 const int ni = rec.n_indels();
-                for (int i = 0; i < ni; ++i) add(rec.indel(i));
+                for (int i = 0; i < ni; ++i) add(raw_indel(i));
                 if (rec.lead() >= 0) add(rec.lead());
                 if (rec.trail() >= 0) add(rec.trail());
             }
@@ -1303,6 +1321,12 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
                 return;
             }
             tab_lo = n_tab ? lo : 0;
+            // (every index of the round's records lies in [tab_lo, tab_lo + n_tab), n_tab <= F5_TAB: 6 bits relative to tab_lo)
+            uint64_t ind = 0;
+#pragma unroll
+            for (int k = 0; k < F5_INDELS; ++k) ind |= uint64_t(unsigned(raw_indel(k) - tab_lo) & 63u) << (6 * k);
+            rec.ind = ind;
+            rec.ind_lo = tab_lo;
             if (lane < n_tab) { // (n_tab <= F5_TAB <= 64: a lane an entry)
                 const PIndel& g = a.job.tab[tab_lo + lane];
                 F5Tab e;
@@ -1347,7 +1371,7 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
         stamp[4] += td - tc; // phase A
         // ---- phase B, a lane its alignment: the terms in path order (f5_sum)
         if (has && !bad) {
-            const double lnp = plain_codes ? f5_sum<true>(S, myslot, n_ent, ln_noncand, ln_quarter) : f5_sum<false>(S, myslot, n_ent, ln_noncand, ln_quarter);
+            const double lnp = f5_sum(S, myslot, n_ent, ln_noncand, ln_quarter);
             fa.scores[c0 + my_j] = lnp;
         }
         stamp[5] += now() - td; // phase B
