@@ -1069,6 +1069,30 @@ int sk_bgzf_inflate_prefixed(const uint8_t* data, const int64_t* block_off, cons
 int sk_bgzf_inflate_dev(const uint8_t* dev_data, const int64_t* dev_block_off, const int64_t* dev_out_off, int32_t n_blocks,
                         uint8_t* dev_out, int32_t* dev_status, void* hip_stream);
 
+/* The other direction: a byte stream goes in, a BGZF stream comes out (csrc/bgzf_deflate.hip, a wave per block).  The input is cut
+ * every SK_BGZF_BLOCK_INPUT bytes (bgzip's cut; the last block is shorter); every block is a complete gzip member with the BGZF extra
+ * field (SAM specification v1, section 4.1: 1f 8b 08 04, MTIME 0, XFL 0, OS ff, XLEN 6, 'B' 'C' 2 0, BSIZE = member length - 1),
+ * ending in the CRC-32 and ISIZE of its input, and is never longer than SK_BGZF_BLOCK_MAX bytes.
+ *   level 0  stored DEFLATE blocks
+ *   level 1  LZ77 (32 KiB window, lengths 3..258, one hash probe, greedy) with the fixed Huffman code
+ *   level 2  the same parse with a dynamic Huffman code built per block
+ * At levels 1 and 2 every block takes the smallest of the encodings its level allows (stored always, fixed at level 2 as well),
+ * chosen from exact bit counts before anything is written: per block, level 2 <= level 1 <= level 0 in size.  The output is a
+ * function of the input and the level alone (two calls give the same bytes).  with_eof appends the 28-byte empty block that ends a
+ * BGZF file; n_bytes == 0 gives that block alone, or nothing. */
+enum { SK_BGZF_BLOCK_INPUT = 65280, SK_BGZF_BLOCK_MAX = 65536 };
+/** Room sk_bgzf_deflate needs for n_bytes of input: every block stored (its bytes + 5 + 26 of framing), plus the EOF block.  Host
+ *  arithmetic only (works without a device); -1 for a negative n_bytes. */
+int64_t sk_bgzf_deflate_bound(int64_t n_bytes, int with_eof);
+/** data[n_bytes] -> out[*out_bytes]; out_cap must be at least sk_bgzf_deflate_bound(n_bytes, with_eof). */
+int sk_bgzf_deflate(const uint8_t* data, int64_t n_bytes, int level, int with_eof, uint8_t* out, int64_t out_cap, int64_t* out_bytes);
+/** The same on device memory.  dev_block_end holds ceil(n_bytes / SK_BGZF_BLOCK_INPUT) + 1 entries: [i] = offset in dev_out where
+ *  member i ends (member i starts where member i - 1 ends, member 0 at 0), the last entry = length of the stream (past the EOF block
+ *  when with_eof) -- what a .gzi or virtual offsets are made of.  The block slots and token streams are scratch of the library's own:
+ *  one deflate call in flight per process. */
+int sk_bgzf_deflate_dev(const uint8_t* dev_data, int64_t n_bytes, int level, int with_eof, uint8_t* dev_out, int64_t out_cap,
+                        int64_t* dev_block_end, void* hip_stream);
+
 typedef struct sk_bam_record { /* bam1_core_t as L/htsapi/bam_record.hh exposes it */
     int32_t ref_id;        /* target_id() */
     int32_t pos;           /* pos() - 1 (0-based, as stored) */

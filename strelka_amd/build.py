@@ -26,6 +26,7 @@ HIP_SOURCES = [
     "csrc/global_align.hip",
     "csrc/read_enumerate.hip",
     "csrc/bam_feed.hip",
+    "csrc/bgzf_deflate.hip",
     "csrc/gvcf_block.hip",
 ]
 HOST_SOURCES = [

@@ -227,7 +227,7 @@ assert DIGT_CALL_DTYPE.itemsize == 144 and SOMATIC_CALL_DTYPE.itemsize == 272
 EXPORTS = [
     "sk_device_count", "sk_host_alloc", "sk_host_free", "sk_init", "sk_init_strict", "sk_check_device_errors", "sk_debug_force_device_libm", "sk_debug_set_g3_variant", "sk_shutdown", "sk_last_error", "sk_version", "sk_is_initialized", "sk_sync_mode", "sk_libm_restated", "sk_broker_client", "sk_broker_enable", "sk_broker_serve", "sk_broker_selftest", "sk_get_qscore_tables",
     "sk_score_alignments", "sk_score_alignments_dev", "sk_align_evmask_words", "sk_align_prepare", "sk_align_colmat_words", "sk_align_prepare_cols",
-    "sk_bgzf_scan", "sk_bgzf_inflate", "sk_bgzf_inflate_prefixed", "sk_bgzf_inflate_dev", "sk_bam_header_end", "sk_bam_scan_records", "sk_bam_decode", "sk_bam_decode_kept", "sk_bam_decode_dev", "sk_normalize_alignments", "sk_normalize_alignments_dev",
+    "sk_bgzf_scan", "sk_bgzf_inflate", "sk_bgzf_inflate_prefixed", "sk_bgzf_inflate_dev", "sk_bgzf_deflate_bound", "sk_bgzf_deflate", "sk_bgzf_deflate_dev", "sk_bam_header_end", "sk_bam_scan_records", "sk_bam_decode", "sk_bam_decode_kept", "sk_bam_decode_dev", "sk_normalize_alignments", "sk_normalize_alignments_dev",
     "sk_align_builder_create", "sk_align_builder_destroy", "sk_align_builder_clear", "sk_align_builder_append", "sk_align_builder_add_read",
     "sk_align_builder_finish", "sk_align_builder_error", "sk_align_builder_set_host_threads",
     "sk_align_scores_default", "sk_global_align",
@@ -317,6 +317,10 @@ def lib():
         L.sk_bgzf_scan.argtypes = [c_void_p, C.c_int64, c_void_p, c_void_p, C.c_int32]
         L.sk_bgzf_inflate.argtypes = [c_void_p, c_void_p, c_void_p, C.c_int32, c_void_p]
         L.sk_bgzf_inflate_dev.argtypes = [c_void_p, c_void_p, c_void_p, C.c_int32, c_void_p, c_void_p, c_void_p]
+        L.sk_bgzf_deflate_bound.restype = C.c_int64
+        L.sk_bgzf_deflate_bound.argtypes = [C.c_int64, C.c_int]
+        L.sk_bgzf_deflate.argtypes = [c_void_p, C.c_int64, C.c_int, C.c_int, c_void_p, C.c_int64, c_void_p]
+        L.sk_bgzf_deflate_dev.argtypes = [c_void_p, C.c_int64, C.c_int, C.c_int, c_void_p, C.c_int64, c_void_p, c_void_p]
         L.sk_bam_header_end.restype = C.c_int64
         L.sk_bam_header_end.argtypes = [c_void_p, C.c_int64]
         L.sk_bam_scan_records.restype = C.c_int64
@@ -1307,6 +1311,21 @@ def bgzf_inflate(data):
     out = np.zeros(int(out_off[-1]), np.uint8)
     _check(lib().sk_bgzf_inflate(_p(data), _p(block_off), _p(out_off), len(block_off) - 1, _p(out)))
     return out
+
+
+def bgzf_deflate_bound(n, with_eof=True):
+    """room bgzf_deflate needs for n input bytes (every block stored, plus the EOF block); host arithmetic, works without a device"""
+    return int(lib().sk_bgzf_deflate_bound(int(n), int(bool(with_eof))))
+
+
+def bgzf_deflate(data, level=2, with_eof=True):
+    """bytes -> a BGZF stream (bytes), compressed on the device: level 0 stored, 1 fixed Huffman code, 2 dynamic codes"""
+    data = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, np.uint8)
+    cap = bgzf_deflate_bound(len(data), with_eof)
+    out = np.empty(max(cap, 1), np.uint8)
+    n_out = C.c_int64(0)
+    _check(lib().sk_bgzf_deflate(_p(data) if len(data) else None, len(data), int(level), int(bool(with_eof)), _p(out), cap, C.byref(n_out)))
+    return out[:n_out.value].tobytes()
 
 
 def bam_scan_records(stream, first=None):
