@@ -6,8 +6,9 @@
     the host one, and per block level 2 <= level 1 <= level 0.
 
 Compressed size of the text fixture (about 300 KB of gVCF-like lines) against zlib level 1 over the same 65 280-byte slices plus 26
-bytes of framing each (56 197 bytes): a Python restatement of the kernel's algorithm (same hash, same turns of 64 positions, same
-parse, same code construction) gives 52 201 bytes at level 2, an excess of -0.071.  NOT yet measured on an MI355X: until it is, the
+bytes of framing each (56 197 bytes): the model of the kernel in tests/deflate_model.py (same hash, same turns of 64 positions, same
+parse, same code construction; tests/test_bgzf_deflate_model.py::test_text_fixture_size_at_level_2 reruns it) gives 52 201 bytes at
+level 2, an excess of -0.071.  NOT yet measured on an MI355X: until it is, the
 margin asserted below is TEXT_MARGIN = 0.00 over zlib's figure (the restatement's excess rounded up to the next 0.05 is -0.05; zero is
 kept until a device run confirms the figure), and test_text_fixture_is_near_zlib_level_1 prints the measured sizes."""
 import functools
@@ -67,8 +68,9 @@ def _window_edge(distance):
 
 
 def _skewed():
-    """byte frequencies that follow the Fibonacci numbers: the unrestricted Huffman code is deeper than 15 bits, so the length limit
-    (and its repair of the Kraft sum) is what gets written"""
+    """byte frequencies that follow the Fibonacci numbers: a deep literal/length code.  It does NOT pass 15 bits (the end of the
+    block is a third leaf of weight 1 and the matcher takes frequent letters into matches: depth 14); the inputs that reach the
+    three length limits are ll_fold, dist_fold and cl_fold of tests/test_bgzf_deflate_model.py"""
     fib = [1, 1]
     while len(fib) < 22:
         fib.append(fib[-1] + fib[-2])
