@@ -1150,6 +1150,76 @@ int sk_normalize_alignments_dev(const char* dev_ref_seq, int32_t ref_offset, int
                                 int32_t* dev_pos, uint8_t* dev_changed, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * The read intake: what addAlignmentIndelsToPosProcessor
+ * (L/starling_common/starling_pos_processor_indel_util.cpp:300-491) derives from a read that does not depend on buffer state, for
+ * the reads sk_bam_decode[_dev] -> sk_normalize_alignments[_dev] leave (the same arrays: the three calls chain on one stream with
+ * no host copy in between), and the active-region detector's per-position counters summed over those reads.
+ *
+ *   per read      the valid range (get_valid_alignment_range, L/starling_common/starling_read_util.cpp:218-329), the function's
+ *                 return value total_indel_ref_span_per_read, and its indel observations: one SK_INDEL_INDEL per simple indel
+ *                 (process_simple_indel :231-296) or swap (process_swap :163-224), a SK_INDEL_BP_LEFT + SK_INDEL_BP_RIGHT pair when
+ *                 longer than max_indel_size; is_noise when the indel's read range (:373-402) is not inside the valid range, cleared
+ *                 for inserts longer than max_cand_filter_insert_size = 10 (:70); edge inserts and deletions give nothing
+ *                 (edge_pin = false, false: genomic reads)
+ *   per position  of [win_begin, win_begin + n_pos): _variantCounter and _depth (ActiveRegionReadBuffer.hh:263-292, .cpp:26-107)
+ *                 as the plain sum over the reads that are not low-MAPQ, and isCandidateVariant (.cpp:258-269) of that sum.  The
+ *                 reference keeps the counters in a ring of 1 000 positions and reads position head - 1
+ *                 (ActiveRegionDetector.cpp:337-353); with the reads in position order and the window covering their span the ring
+ *                 holds this sum at that moment.  Contributions outside the window are dropped.
+ *
+ * Out of scope: pinned edges (RNA); externally supplied candidate or forced indels (they do not come from reads); the per-read
+ * haplotype store (setMatch, _positionToAlignIds, getReadSegments); the repeat finder; IndelBuffer bookkeeping.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct sk_intake_options {
+    uint32_t max_indel_size;        /* starling_base_options::maxIndelSize */
+    float min_alt_allele_fraction;  /* ActiveRegionDetector::MinAlternativeAlleleFraction */
+} sk_intake_options;
+/** The reference's defaults: max_indel_size 49 (L/starling_common/starling_base_shared.hh:124), min_alt_allele_fraction 0.2f
+ *  (L/starling_common/ActiveRegionDetector.hh:68). */
+void sk_intake_options_default(sk_intake_options* o);
+typedef struct sk_intake_read {
+    int32_t valid_begin, valid_end;  /* get_valid_alignment_range: read positions; (0, 0) when it comes out empty (:324-328) */
+    uint32_t total_indel_ref_span;   /* addAlignmentIndelsToPosProcessor's return value (:341, :384, :397) */
+    uint32_t n_obs;
+} sk_intake_read;
+typedef struct sk_intake_obs { /* IndelObservation as insert_indel receives it (:45-52) */
+    int32_t read;                /* index of the read in the call */
+    int32_t pos;                 /* key.pos */
+    uint32_t deletion_length;    /* key.deletionLength */
+    uint32_t ins_begin, ins_len; /* key.insertSequence as a range of the read's bases; (0, 0) when empty */
+    uint32_t bp_begin, bp_len;   /* data.breakpointInsertionSequence, likewise (:205-208, :216-218, :278-281, :290-292) */
+    uint8_t type;                /* SK_INDEL_INDEL, SK_INDEL_BP_LEFT or SK_INDEL_BP_RIGHT */
+    uint8_t is_noise;            /* data.is_noise (:402, :182-188, :249-256) */
+    uint8_t is_low_mapq;         /* data.is_low_map_quality (:368) */
+    uint8_t pad;
+} sk_intake_obs;
+typedef struct sk_intake_site { /* ActiveRegionReadBuffer::_variantCounter, _depth (ActiveRegionReadBuffer.hh:232-236) */
+    uint32_t variant_count, depth;
+} sk_intake_site;
+/** Room for the observations of paths of n_path_segments segments in all: 2 per segment.  Host arithmetic only (works without a
+ *  device); -1 for a negative count. */
+int64_t sk_read_intake_obs_bound(int64_t n_path_segments);
+/** Read r: bases read_code[read_off[r] .. read_off[r + 1]), alignment pos[r] + path[path_off[r] .. path_off[r] + n_seg[r]), low_mapq[r]
+ *  != 0 for a read of MAPQ 0 (isLowMapQuality, L/starling_common/starling_pos_processor_base.cpp:666).  reads[n_reads]; obs_off[n_reads
+ *  + 1]: the observations of read r are obs[obs_off[r] .. obs_off[r + 1]), in path order, BP_LEFT before BP_RIGHT; obs_cap must be at
+ *  least sk_read_intake_obs_bound(path_off[n_reads]); sites[n_pos], is_candidate[n_pos].  Refused with a message: a read longer than
+ *  SK_PILEUP_MAX_READ_LEN, a path is_apath_invalid / is_apath_starling_invalid (L/blt_util/align_path.cpp:928-1013) would reject, a SKIP
+ *  or zero-length segment, a path whose read length is not the read_off span, obs_cap below the bound, negative sizes. */
+int sk_read_intake(const char* ref_seq, int32_t ref_offset, int32_t ref_len, int32_t n_reads, const int64_t* read_off, const uint8_t* read_code,
+                   const int64_t* path_off, const int32_t* n_seg, const sk_path_seg* path, const int32_t* pos, const uint8_t* low_mapq,
+                   const sk_intake_options* opt, int32_t win_begin, int32_t n_pos, sk_intake_read* reads, int64_t* obs_off, sk_intake_obs* obs,
+                   int64_t obs_cap, sk_intake_site* sites, uint8_t* is_candidate);
+/** The same on device memory (opt is read on the host); only enqueues.  dev_sites must be 8-byte aligned.  Input the host entry
+ *  would refuse raises the sticky device flag instead (sk_check_device_errors); such a read's record is zero. */
+int sk_read_intake_dev(const char* dev_ref_seq, int32_t ref_offset, int32_t ref_len, int32_t n_reads, const int64_t* dev_read_off,
+                       const uint8_t* dev_read_code, const int64_t* dev_path_off, const int32_t* dev_n_seg, const sk_path_seg* dev_path,
+                       const int32_t* dev_pos, const uint8_t* dev_low_mapq, const sk_intake_options* opt, int32_t win_begin, int32_t n_pos,
+                       sk_intake_read* dev_reads, int64_t* dev_obs_off, sk_intake_obs* dev_obs, int64_t obs_cap, sk_intake_site* dev_sites,
+                       uint8_t* dev_is_candidate, void* dev_scratch, size_t scratch_bytes, void* hip_stream);
+/** Bytes of device scratch sk_read_intake_dev needs.  Host arithmetic only. */
+size_t sk_read_intake_scratch_bytes(int32_t n_reads, int64_t n_path_segments, int32_t n_pos);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * SURVEY.md section 8f rank 4, the output side: the non-variant blocks of the gVCF.
  *
  * gvcf_writer::queue_site_record (L/applications/starling/gvcf_writer.cpp:278-302) asks, site after site and per sample, whether the

@@ -27,6 +27,7 @@ HIP_SOURCES = [
     "csrc/read_enumerate.hip",
     "csrc/bam_feed.hip",
     "csrc/bgzf_deflate.hip",
+    "csrc/read_intake.hip",
     "csrc/gvcf_block.hip",
 ]
 HOST_SOURCES = [

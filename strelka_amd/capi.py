@@ -100,6 +100,10 @@ class GlobalAlignBatch(C.Structure):
     _fields_ = [("n", C.c_int32), ("query_off", c_void_p), ("query", c_void_p), ("ref_off", c_void_p), ("ref", c_void_p)]
 
 
+class IntakeOptions(C.Structure):
+    _fields_ = [("max_indel_size", C.c_uint32), ("min_alt_allele_fraction", C.c_float)]
+
+
 class PileupOptions(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("min_basecall_qscore", "mismatch_density_flank_size", "mismatch_density_max_count",
                                          "use_tier2_evidence", "tier2_mismatch_density_max_count", "is_mapq_adjust",
@@ -228,6 +232,7 @@ EXPORTS = [
     "sk_device_count", "sk_host_alloc", "sk_host_free", "sk_init", "sk_init_strict", "sk_check_device_errors", "sk_debug_force_device_libm", "sk_debug_set_g3_variant", "sk_shutdown", "sk_last_error", "sk_version", "sk_is_initialized", "sk_sync_mode", "sk_libm_restated", "sk_broker_client", "sk_broker_enable", "sk_broker_serve", "sk_broker_selftest", "sk_get_qscore_tables",
     "sk_score_alignments", "sk_score_alignments_dev", "sk_align_evmask_words", "sk_align_prepare", "sk_align_colmat_words", "sk_align_prepare_cols",
     "sk_bgzf_scan", "sk_bgzf_inflate", "sk_bgzf_inflate_prefixed", "sk_bgzf_inflate_dev", "sk_bgzf_deflate_bound", "sk_bgzf_deflate", "sk_bgzf_deflate_dev", "sk_bam_header_end", "sk_bam_scan_records", "sk_bam_decode", "sk_bam_decode_kept", "sk_bam_decode_dev", "sk_normalize_alignments", "sk_normalize_alignments_dev",
+    "sk_intake_options_default", "sk_read_intake_obs_bound", "sk_read_intake", "sk_read_intake_dev", "sk_read_intake_scratch_bytes",
     "sk_align_builder_create", "sk_align_builder_destroy", "sk_align_builder_clear", "sk_align_builder_append", "sk_align_builder_add_read",
     "sk_align_builder_finish", "sk_align_builder_error", "sk_align_builder_set_host_threads",
     "sk_align_scores_default", "sk_global_align",
@@ -329,6 +334,16 @@ def lib():
         L.sk_bam_decode_dev.argtypes = [c_void_p, c_void_p, C.c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
         L.sk_normalize_alignments.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32] + [c_void_p] * 7
         L.sk_normalize_alignments_dev.argtypes = [c_void_p, C.c_int32, C.c_int32, C.c_int32] + [c_void_p] * 8
+        L.sk_intake_options_default.argtypes = [C.POINTER(IntakeOptions)]
+        L.sk_intake_options_default.restype = None
+        L.sk_read_intake_obs_bound.restype = C.c_int64
+        L.sk_read_intake_obs_bound.argtypes = [C.c_int64]
+        L.sk_read_intake_scratch_bytes.restype = C.c_size_t
+        L.sk_read_intake_scratch_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int32]
+        L.sk_read_intake.argtypes = [c_void_p, C.c_int32, C.c_int32, C.c_int32] + [c_void_p] * 7 + [C.POINTER(IntakeOptions), C.c_int32, C.c_int32,
+                                     c_void_p, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p]
+        L.sk_read_intake_dev.argtypes = [c_void_p, C.c_int32, C.c_int32, C.c_int32] + [c_void_p] * 7 + [C.POINTER(IntakeOptions), C.c_int32, C.c_int32,
+                                         c_void_p, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p, c_void_p, C.c_size_t, c_void_p]
         L.sk_align_colmat_words.restype = C.c_int64
         L.sk_align_colmat_words.argtypes = [c_void_p]
         L.sk_align_prepare_cols.argtypes = [c_void_p] * 4
@@ -1386,6 +1401,66 @@ def normalize_alignments(ref_seq, ref_offset, reads, library=None):
         seg = path[int(path_off[i]):int(path_off[i]) + int(n_seg[i])]
         out.append((int(changed[i]), int(pos[i]), [(int(t), int(l)) for t, l in seg]))
     return out
+
+
+INTAKE_READ_DTYPE = np.dtype([("valid_begin", "<i4"), ("valid_end", "<i4"), ("total_indel_ref_span", "<u4"), ("n_obs", "<u4")])
+INTAKE_OBS_DTYPE = np.dtype([("read", "<i4"), ("pos", "<i4"), ("deletion_length", "<u4"), ("ins_begin", "<u4"), ("ins_len", "<u4"), ("bp_begin", "<u4"),
+                             ("bp_len", "<u4"), ("type", "u1"), ("is_noise", "u1"), ("is_low_mapq", "u1"), ("pad", "u1")])
+INTAKE_SITE_DTYPE = np.dtype([("variant_count", "<u4"), ("depth", "<u4")])
+assert INTAKE_READ_DTYPE.itemsize == 16 and INTAKE_OBS_DTYPE.itemsize == 32 and INTAKE_SITE_DTYPE.itemsize == 8
+
+
+def intake_options():
+    o = IntakeOptions()
+    lib().sk_intake_options_default(C.byref(o))
+    return o
+
+
+def read_intake_obs_bound(n_path_segments):
+    """room for the observations of paths of n_path_segments segments in all; host arithmetic, works without a device"""
+    return int(lib().sk_read_intake_obs_bound(int(n_path_segments)))
+
+
+def pack_reads(reads):
+    """reads: dicts(code uint8[], pos, path [(type, length)]) -> (read_off, code, path_off, n_seg, path, pos): the arrays
+    sk_normalize_alignments and sk_read_intake take"""
+    n = len(reads)
+    read_off = np.zeros(n + 1, np.int64)
+    path_off = np.zeros(n + 1, np.int64)
+    for i, r in enumerate(reads):
+        read_off[i + 1] = read_off[i] + len(r["code"])
+        path_off[i + 1] = path_off[i] + len(r["path"])
+    code = np.concatenate([np.asarray(r["code"], np.uint8) for r in reads] + [np.zeros(1, np.uint8)])
+    path = np.zeros(max(int(path_off[-1]), 1), PATH_SEG_DTYPE)
+    k = 0
+    for r in reads:
+        for t, l in r["path"]:
+            path[k] = (t, l)
+            k += 1
+    n_seg = np.array([len(r["path"]) for r in reads] + [0], np.int32)
+    pos = np.array([r["pos"] for r in reads] + [0], np.int32)
+    return read_off, code, path_off, n_seg, path, pos
+
+
+def read_intake(ref_seq, ref_offset, reads, low_mapq, win_begin, n_pos, opt=None):
+    """reads: the form normalize_alignments takes; low_mapq: one flag per read -> dict(reads[INTAKE_READ_DTYPE], obs_off,
+    obs[INTAKE_OBS_DTYPE], sites[INTAKE_SITE_DTYPE], is_candidate bool[]) through sk_read_intake"""
+    L = lib()
+    n = len(reads)
+    read_off, code, path_off, n_seg, path, pos = pack_reads(reads)
+    low = np.zeros(n + 1, np.uint8)
+    low[:n] = np.asarray(low_mapq, np.uint8)[:n] != 0
+    opt = opt or intake_options()
+    cap = read_intake_obs_bound(int(path_off[-1]))
+    rec = np.zeros(max(n, 1), INTAKE_READ_DTYPE)
+    obs_off = np.zeros(n + 1, np.int64)
+    obs = np.zeros(max(cap, 1), INTAKE_OBS_DTYPE)
+    sites = np.zeros(max(n_pos, 1), INTAKE_SITE_DTYPE)
+    cand = np.zeros(max(n_pos, 1), np.uint8)
+    ref_b = ref_seq.encode() if isinstance(ref_seq, str) else bytes(ref_seq)
+    _check(L.sk_read_intake(ref_b, int(ref_offset), len(ref_b), n, _p(read_off), _p(code), _p(path_off), _p(n_seg), _p(path), _p(pos), _p(low),
+                            C.byref(opt), int(win_begin), int(n_pos), _p(rec), _p(obs_off), _p(obs), cap, _p(sites), _p(cand)))
+    return dict(reads=rec[:n], obs_off=obs_off, obs=obs[:int(obs_off[-1])], sites=sites[:n_pos], is_candidate=cand[:n_pos].astype(bool))
 
 
 BAI_CHUNK_DTYPE = np.dtype([("begin", "<u8"), ("end", "<u8")])

@@ -61,7 +61,10 @@ struct SkContext
     size_t global_align_lds_allowed = 0;
     bool inflate_scalar_lds_allowed = false;
 };
-enum { SK_DEVERR_QSCORE = 1u }; // a basecall quality above 70 reached a scoring kernel (qscore_cache.cpp:53-75 throws)
+enum {
+    SK_DEVERR_QSCORE = 1u, // a basecall quality above 70 reached a scoring kernel (qscore_cache.cpp:53-75 throws)
+    SK_DEVERR_INTAKE = 2u  // sk_read_intake_dev met a read or path its host entry refuses, or ran out of obs_cap
+};
 
 SkContext& sk_ctx();
 void sk_set_error(const std::string& msg);

@@ -400,6 +400,8 @@ int sk_check_device_errors(void)
     SK_HIP(skrt::memset_(c.dev_error_flags, 0, sizeof(unsigned)));
     if (flags & SK_DEVERR_QSCORE)
         return sk_fail("Attempting to lookup basecall quality score which exceeds the maximum cached score of 70 (seen by a *_dev kernel)");
+    if (flags & SK_DEVERR_INTAKE)
+        return sk_fail("sk_read_intake_dev: a read longer than SK_PILEUP_MAX_READ_LEN, a path whose read length is not the read_off span, or obs_cap too small");
     return sk_fail("strelka_amd: a kernel reported an error");
 }
 
