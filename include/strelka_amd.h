@@ -1220,6 +1220,68 @@ int sk_read_intake_dev(const char* dev_ref_seq, int32_t ref_offset, int32_t ref_
 size_t sk_read_intake_scratch_bytes(int32_t n_reads, int64_t n_path_segments, int32_t n_pos);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Active regions (second half): what the reference spends the intake's per-position arrays on.
+ *
+ *   anchors   ReferenceRepeatFinder (L/starling_common/ReferenceRepeatFinder.cpp:26-80; constants MaxRepeatUnitLength = 50,
+ *             MinRepeatSpan = 3, a ring of MaxBufferSize = 1000 positions, ActiveRegionReadBuffer.hh:61-74): which reference
+ *             positions lie outside any short tandem repeat.  A function of the reference sequence, of the position the finder was
+ *             initialised at (initRepeatSpan :60-80, called by ActiveRegionReadBuffer::setEndPos, ActiveRegionReadBuffer.cpp:173-189)
+ *             and of 50 stale values: initRepeatSpan writes the spans of its first position m = max(init_pos - 99, ref_offset) and
+ *             updateRepeatSpan(m) overwrites them from ring slot (m - 1) % 1000, which holds zeros in a fresh finder and otherwise
+ *             whatever an earlier region left there.
+ *   the walk  SampleActiveRegionDetector::updateEndPosition (L/starling_common/ActiveRegionDetector.cpp:336-409) and createActiveRegion
+ *             (:314-328), constants MaxDistanceBetweenTwoVariants = 13, MinNumVariantsPerRegion = 2 (ActiveRegionDetector.hh:141-144):
+ *             (candidate?, depth zero?, anchor?) per position -> active regions.
+ *
+ * On one stream sk_read_intake_dev -> sk_ref_anchors_dev -> sk_active_regions_dev run with no host copy in between.
+ * Out of scope: closeActiveRegionDetector (:413-, it needs the read buffer's range; the caller's, from state_out), the multi-sample
+ * synchroniser (ActiveRegionDetector::updateEndPosition, processExistingActiveRegion, closeActiveRegion), external or forced
+ * candidates (callers may edit is_candidate and sites before the walk), getReadSegments.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define SK_REPEAT_MAX_UNIT 50
+typedef struct sk_ar_state { /* SampleActiveRegionDetector's coordinates, ActiveRegionDetector.hh:201-215 */
+    int32_t is_beginning, active_region_start_pos, anchor_pos_following_prev_variant, prev_anchor_pos, prev_variant_pos;
+    uint32_t num_variants;
+} sk_ar_state;
+/** The constructor's / clearCoordinates' values (ActiveRegionDetector.hh:157-158, .cpp:296-303): is_beginning = 1, the positions -1,
+ *  num_variants 0. */
+void sk_ar_state_initial(sk_ar_state* s);
+typedef struct sk_active_region { /* [begin, end) as createActiveRegion returns it (.cpp:327) */
+    int32_t begin, end;
+    int32_t made_at; /* the pos argument of the updateEndPosition call that returned it */
+} sk_active_region;
+/** is_anchor[i]: what ReferenceRepeatFinder::isAnchor(win_begin + i) (ReferenceRepeatFinder.hh:54-57) returns once the finder has
+ *  been updated through win_begin + i + 101 -- the moment the detector reads it (ActiveRegionDetector.cpp:339, :362) -- in a finder
+ *  initialised by initRepeatSpan(init_pos) whose ring slot (m - 1) % 1000 held init_span[50] (NULL: zeros, a fresh finder).
+ *  span_out[k][50]: the _repeatSpan row (ReferenceRepeatFinder.cpp:42) of position span_pos[k] >= m, for carrying the stale slot
+ *  across regions.  Refused with a message: win_begin or a span_pos before m, negative sizes or ref_offset, a position beyond int32's
+ *  reach of the finder's arithmetic (pos + 100). */
+int sk_ref_anchors(const char* ref_seq, int32_t ref_offset, int32_t ref_len, int32_t init_pos, const uint32_t* init_span, int32_t win_begin,
+                   int32_t n_pos, uint8_t* is_anchor, int32_t n_span_pos, const int32_t* span_pos, uint32_t* span_out);
+/** The same on device memory (init_span is read on the host); only enqueues.  A span_pos before m raises the sticky device flag
+ *  (sk_check_device_errors) and gives a row of zeros. */
+int sk_ref_anchors_dev(const char* dev_ref_seq, int32_t ref_offset, int32_t ref_len, int32_t init_pos, const uint32_t* init_span, int32_t win_begin,
+                       int32_t n_pos, uint8_t* dev_is_anchor, int32_t n_span_pos, const int32_t* dev_span_pos, uint32_t* dev_span_out,
+                       void* hip_stream);
+/** Room for the regions of a window of n_pos positions: n_pos / 2 + 1.  Host arithmetic only (works without a device); -1 for a
+ *  negative count. */
+int64_t sk_active_regions_bound(int32_t n_pos);
+/** The calls updateEndPosition(pos) for pos = win_begin + 1 .. win_begin + n_pos (ActiveRegionDetector.cpp:336-409), which process
+ *  the positions win_begin .. win_begin + n_pos - 1: sites[i].depth == 0 is isDepthZero (:354), is_candidate[i] isCandidateVariant
+ *  (:353) as sk_read_intake leaves them, is_anchor[i] as sk_ref_anchors does.  regions[0 .. *n_regions) in the order the calls return
+ *  them; windows chain through state_in / state_out (they may be the same object).  Refused with a message: region_cap below
+ *  sk_active_regions_bound(n_pos), win_begin < 0, negative sizes, a state_in on which createActiveRegion's assertion (:318) would
+ *  fail at once (two variants or more, an anchor after them, and a start not before it); where the assertion fails mid-window the
+ *  call fails and emits nothing. */
+int sk_active_regions(int32_t win_begin, int32_t n_pos, const sk_intake_site* sites, const uint8_t* is_candidate, const uint8_t* is_anchor,
+                      const sk_ar_state* state_in, sk_ar_state* state_out, sk_active_region* regions, int64_t region_cap, int32_t* n_regions);
+/** The same on device memory, state_in / state_out / n_regions included; only enqueues.  Where createActiveRegion's assertion fails
+ *  the sticky device flag is raised (sk_check_device_errors), n_regions is 0 and state_out = state_in. */
+int sk_active_regions_dev(int32_t win_begin, int32_t n_pos, const sk_intake_site* dev_sites, const uint8_t* dev_is_candidate,
+                          const uint8_t* dev_is_anchor, const sk_ar_state* dev_state_in, sk_ar_state* dev_state_out,
+                          sk_active_region* dev_regions, int64_t region_cap, int32_t* dev_n_regions, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * SURVEY.md section 8f rank 4, the output side: the non-variant blocks of the gVCF.
  *
  * gvcf_writer::queue_site_record (L/applications/starling/gvcf_writer.cpp:278-302) asks, site after site and per sample, whether the

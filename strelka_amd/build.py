@@ -28,6 +28,7 @@ HIP_SOURCES = [
     "csrc/bam_feed.hip",
     "csrc/bgzf_deflate.hip",
     "csrc/read_intake.hip",
+    "csrc/active_region_detect.hip",
     "csrc/gvcf_block.hip",
 ]
 HOST_SOURCES = [

@@ -233,6 +233,7 @@ EXPORTS = [
     "sk_score_alignments", "sk_score_alignments_dev", "sk_align_evmask_words", "sk_align_prepare", "sk_align_colmat_words", "sk_align_prepare_cols",
     "sk_bgzf_scan", "sk_bgzf_inflate", "sk_bgzf_inflate_prefixed", "sk_bgzf_inflate_dev", "sk_bgzf_deflate_bound", "sk_bgzf_deflate", "sk_bgzf_deflate_dev", "sk_bam_header_end", "sk_bam_scan_records", "sk_bam_decode", "sk_bam_decode_kept", "sk_bam_decode_dev", "sk_normalize_alignments", "sk_normalize_alignments_dev",
     "sk_intake_options_default", "sk_read_intake_obs_bound", "sk_read_intake", "sk_read_intake_dev", "sk_read_intake_scratch_bytes",
+    "sk_ar_state_initial", "sk_ref_anchors", "sk_ref_anchors_dev", "sk_active_regions_bound", "sk_active_regions", "sk_active_regions_dev",
     "sk_align_builder_create", "sk_align_builder_destroy", "sk_align_builder_clear", "sk_align_builder_append", "sk_align_builder_add_read",
     "sk_align_builder_finish", "sk_align_builder_error", "sk_align_builder_set_host_threads",
     "sk_align_scores_default", "sk_global_align",
@@ -344,6 +345,14 @@ def lib():
                                      c_void_p, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p]
         L.sk_read_intake_dev.argtypes = [c_void_p, C.c_int32, C.c_int32, C.c_int32] + [c_void_p] * 7 + [C.POINTER(IntakeOptions), C.c_int32, C.c_int32,
                                          c_void_p, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p, c_void_p, C.c_size_t, c_void_p]
+        L.sk_ar_state_initial.argtypes = [c_void_p]
+        L.sk_ar_state_initial.restype = None
+        L.sk_active_regions_bound.restype = C.c_int64
+        L.sk_active_regions_bound.argtypes = [C.c_int32]
+        L.sk_ref_anchors.argtypes = [c_void_p, C.c_int32, C.c_int32, C.c_int32, c_void_p, C.c_int32, C.c_int32, c_void_p, C.c_int32, c_void_p, c_void_p]
+        L.sk_ref_anchors_dev.argtypes = L.sk_ref_anchors.argtypes + [c_void_p]
+        L.sk_active_regions.argtypes = [C.c_int32, C.c_int32] + [c_void_p] * 6 + [C.c_int64, c_void_p]
+        L.sk_active_regions_dev.argtypes = L.sk_active_regions.argtypes + [c_void_p]
         L.sk_align_colmat_words.restype = C.c_int64
         L.sk_align_colmat_words.argtypes = [c_void_p]
         L.sk_align_prepare_cols.argtypes = [c_void_p] * 4
@@ -1461,6 +1470,63 @@ def read_intake(ref_seq, ref_offset, reads, low_mapq, win_begin, n_pos, opt=None
     _check(L.sk_read_intake(ref_b, int(ref_offset), len(ref_b), n, _p(read_off), _p(code), _p(path_off), _p(n_seg), _p(path), _p(pos), _p(low),
                             C.byref(opt), int(win_begin), int(n_pos), _p(rec), _p(obs_off), _p(obs), cap, _p(sites), _p(cand)))
     return dict(reads=rec[:n], obs_off=obs_off, obs=obs[:int(obs_off[-1])], sites=sites[:n_pos], is_candidate=cand[:n_pos].astype(bool))
+
+
+REPEAT_MAX_UNIT = 50
+AR_STATE_DTYPE = np.dtype([("is_beginning", "<i4"), ("active_region_start_pos", "<i4"), ("anchor_pos_following_prev_variant", "<i4"),
+                           ("prev_anchor_pos", "<i4"), ("prev_variant_pos", "<i4"), ("num_variants", "<u4")])
+ACTIVE_REGION_DTYPE = np.dtype([("begin", "<i4"), ("end", "<i4"), ("made_at", "<i4")])
+assert AR_STATE_DTYPE.itemsize == 24 and ACTIVE_REGION_DTYPE.itemsize == 12
+
+
+def ar_state_initial():
+    """SampleActiveRegionDetector's coordinates as its constructor leaves them -> AR_STATE_DTYPE[1]"""
+    s = np.zeros(1, AR_STATE_DTYPE)
+    lib().sk_ar_state_initial(_p(s))
+    return s
+
+
+def ar_state(values):
+    """dict of the six fields (or an AR_STATE_DTYPE record) -> AR_STATE_DTYPE[1]"""
+    s = np.zeros(1, AR_STATE_DTYPE)
+    for k in AR_STATE_DTYPE.names:
+        s[k][0] = values[k]
+    return s
+
+
+def active_regions_bound(n_pos):
+    """room for the regions of a window of n_pos positions; host arithmetic, works without a device"""
+    return int(lib().sk_active_regions_bound(int(n_pos)))
+
+
+def ref_anchors(ref_seq, ref_offset, init_pos, init_span, win_begin, n_pos, span_pos=()):
+    """-> (is_anchor uint8[n_pos], span rows uint32[len(span_pos)][50]) through sk_ref_anchors; init_span: 50 values or None (a fresh finder)"""
+    ref_b = ref_seq.encode() if isinstance(ref_seq, str) else bytes(ref_seq)
+    init = None if init_span is None else np.ascontiguousarray(init_span, np.uint32)
+    assert init is None or len(init) == REPEAT_MAX_UNIT
+    sp = np.ascontiguousarray(list(span_pos) + [0], np.int32)
+    anchor = np.zeros(max(int(n_pos), 1), np.uint8)
+    rows = np.zeros((max(len(span_pos), 1), REPEAT_MAX_UNIT), np.uint32)
+    _check(lib().sk_ref_anchors(ref_b, int(ref_offset), len(ref_b), int(init_pos), _p(init), int(win_begin), int(n_pos), _p(anchor), len(span_pos), _p(sp), _p(rows)))
+    return anchor[:max(int(n_pos), 0)], rows[:len(span_pos)]
+
+
+def active_regions(win_begin, sites, is_candidate, is_anchor, state=None, region_cap=None):
+    """sites: INTAKE_SITE_DTYPE[n_pos]; state: AR_STATE_DTYPE[1] or None (the initial one) -> (regions ACTIVE_REGION_DTYPE[], state_out
+    AR_STATE_DTYPE[1]) through sk_active_regions"""
+    sites = np.ascontiguousarray(sites, INTAKE_SITE_DTYPE)
+    n = len(sites)
+    cand = np.ascontiguousarray(np.asarray(is_candidate).astype(np.uint8))
+    anchor = np.ascontiguousarray(np.asarray(is_anchor).astype(np.uint8))
+    assert len(cand) == n and len(anchor) == n
+    state_in = ar_state_initial() if state is None else np.ascontiguousarray(state, AR_STATE_DTYPE)
+    state_out = np.zeros(1, AR_STATE_DTYPE)
+    cap = active_regions_bound(n) if region_cap is None else int(region_cap)
+    regions = np.zeros(max(cap, 1), ACTIVE_REGION_DTYPE)
+    n_regions = np.zeros(1, np.int32)
+    _check(lib().sk_active_regions(int(win_begin), n, _p(sites) if n else None, _p(cand) if n else None, _p(anchor) if n else None, _p(state_in), _p(state_out),
+                                   _p(regions), cap, _p(n_regions)))
+    return regions[:int(n_regions[0])], state_out
 
 
 BAI_CHUNK_DTYPE = np.dtype([("begin", "<u8"), ("end", "<u8")])

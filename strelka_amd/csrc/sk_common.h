@@ -63,7 +63,8 @@ struct SkContext
 };
 enum {
     SK_DEVERR_QSCORE = 1u, // a basecall quality above 70 reached a scoring kernel (qscore_cache.cpp:53-75 throws)
-    SK_DEVERR_INTAKE = 2u  // sk_read_intake_dev met a read or path its host entry refuses, or ran out of obs_cap
+    SK_DEVERR_INTAKE = 2u, // sk_read_intake_dev met a read or path its host entry refuses, or ran out of obs_cap
+    SK_DEVERR_ACTIVE_REGION = 4u // sk_active_regions_dev: createActiveRegion's assertion failed; sk_ref_anchors_dev: a span_pos before m
 };
 
 SkContext& sk_ctx();
