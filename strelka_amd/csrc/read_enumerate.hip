@@ -436,12 +436,37 @@ __device__ inline uint8_t code_of(const char c) // get_bam_seq_code, L/htsapi/ba
     default: return SK_BAM_ANY;
     }
 }
+// the same on the host, as a table: the job's code images (FlatArgs::ref_code, ins_code) are made with it
+constexpr int F5_CODE_PAD = 1024; // bytes of SK_BAM_ANY on either side of the reference's codes
+struct CodeLut
+{
+    uint8_t code[256];
+    CodeLut()
+    {
+        std::memset(code, SK_BAM_ANY, sizeof(code));
+        code[uint8_t('=')] = SK_BAM_REF;
+        code[uint8_t('A')] = SK_BAM_A;
+        code[uint8_t('C')] = SK_BAM_C;
+        code[uint8_t('G')] = SK_BAM_G;
+        code[uint8_t('T')] = SK_BAM_T;
+    }
+};
+inline const CodeLut& code_lut()
+{
+    static const CodeLut l;
+    return l;
+}
 
 struct FlatArgs
 {
     PJob job;
     const char* ins_pool;
     const char* ref;
+    // the job's code images (F5 reads these; the staged chain keeps reading the characters): code_of() of every reference character
+    // with F5_CODE_PAD bytes of SK_BAM_ANY before and after it (ref_code points at the reference's first base: a window that leaves
+    // the reference reads pad), and of every character of the insert pool
+    const uint8_t* ref_code;
+    const uint8_t* ins_code;
     int32_t ref_offset, ref_len;
     int32_t n_reads, n_cals;
     const PCal* pool;
@@ -812,9 +837,10 @@ constexpr int F5_MAX_POOL = 768;
 #ifndef F5_SORT
 #define F5_SORT 1 // experiments: 0 = the set's order
 #endif
-constexpr int F5_TAB = 32;       // span of table indices the indels of one round's candidate alignments may cover
+constexpr int F5_TAB = 32;       // span of table indices the indels of one round's candidate alignments may cover (and the width of the
+                                 // mask the round's consulted entries are gathered in: 32 bits, a bit an entry of the copy)
 
-static_assert(F5_TAB <= 64, "the table copy is a lane an entry");
+static_assert(F5_TAB <= 32, "the table copy is a lane an entry, the consulted mask a bit an entry");
 
 struct FusedScoreArgs
 {
@@ -865,10 +891,16 @@ struct F5Lds
 };
 // (the CU hands LDS out in 1 280-byte pieces: 10 240 bytes are sixteen waves to a CU, one byte more fourteen; the 256-base form,
 // ~12.4 KB, still fits three four-wave blocks)
-static_assert(sizeof(F5Lds<152>) <= 10240, "sixteen waves of the short-read form to a CU");
-static_assert(3 * 4 * sizeof(F5Lds<F5_MAX_READ>) <= 160 * 1024, "three four-wave blocks of the long-read form to a CU");
+constexpr int F5_Q_TERMS = 2 * (SK_NQ + 1); // the block's copy of q2lncompe and q2mis
+constexpr size_t f5_block_granules(const size_t lds_object, const int waves) // a block's LDS in the CU's 1 280-byte pieces (128 to a CU)
+{
+    return (lds_object * size_t(waves) + 8 * size_t(F5_Q_TERMS) + 1279) / 1280;
+}
+static_assert(sizeof(F5Lds<152>) <= 10240 && 2 * f5_block_granules(sizeof(F5Lds<152>), 8) <= 128, "two eight-wave blocks of the short-read form to a CU");
+static_assert(3 * f5_block_granules(sizeof(F5Lds<F5_MAX_READ>), 4) <= 128, "three four-wave blocks of the long-read form to a CU");
 static_assert((152 + 12) % 4 == 0 && (F5_MAX_READ + 12) % 4 == 0 && (F5_MAX_POOL + 12) % 4 == 0, "the byte arrays' words stay aligned");
 static_assert(INS_CAP <= 64, "a lane an insert");
+static_assert(F5_CODE_PAD >= F5_MAX_POOL + 16 && F5_CODE_PAD % 4 == 0, "a window that leaves the reference stays inside the pad");
 
 // A compact record's path in the lane's registers: the walk looks at a segment's type up to a dozen times per turn (the edge
 // segments, the look-ahead for swaps, the step to the next segment) and every look from LDS is a round trip on the lane's chain.  The
@@ -890,7 +922,7 @@ struct F5Rec
     __device__ __forceinline__ int n_indels() const { return int((w2 >> 16) & 0xffu); }
     __device__ __forceinline__ int indel(const int k) const { return ind_lo + int(unsigned(ind >> (6 * k)) & 63u); }
 };
-static_assert(F5_TAB <= 64 && 6 * F5_INDELS <= 64, "an indel index in 6 bits, eight in one value");
+static_assert(6 * F5_INDELS <= 64, "an indel index in 6 bits, eight in one value");
 
 // flatten_cal over a compact record, every look-up from the block's LDS copies: the walk of scoreCandidateAlignment :286-493 as
 // host/align_flatten.cpp states it, as ONE loop of selects.  Written with the reference's four branches (swap, sequence mismatch, insert,
@@ -902,7 +934,7 @@ static_assert(F5_TAB <= 64 && 6 * F5_INDELS <= 64, "an indel index in 6 bits, ei
 // Only a swap (insert + delete run: rare) keeps a branch of its own.  The walk writes the alignment's transitions into its slot:
 // one word per op that covers read positions and one for the read's end; returns their number, -1 = leave the read to the host form.
 template <typename LDS>
-__device__ __forceinline__ int f5_walk_selects(LDS& S, const F5Rec c, const bool has, const int tab_lo, const int32_t win_begin, uint8_t* consulted,
+__device__ __forceinline__ int f5_walk_selects(LDS& S, const F5Rec c, const bool has, const int tab_lo, const int32_t win_begin, uint32_t& consulted,
                                                const int32_t L, const int32_t P, uint32_t* const myslot)
 {
     constexpr uint64_t N1 = 0x1111111111111111ull;
@@ -999,7 +1031,7 @@ __device__ __forceinline__ int f5_walk_selects(LDS& S, const F5Rec c, const bool
         const bool key_ok = key >= 0;
         const F5Tab te = S.tab[(key_ok ? key : tab_lo) - tab_lo];
         const bool indel_ok = live && is_indel_seg && key_ok;
-        if (indel_ok && consulted) consulted[key] = 1; // job_cand
+        consulted |= indel_ok ? (1u << ((key - tab_lo) & 31)) : 0u; // job_cand: bit key - tab_lo (the copy holds F5_TAB <= 32 entries)
         const bool pen = is_indel_seg && (te.type_cand >> 8) == 0u;
         const int32_t head = (pi < ends_first) ? int32_t(te.ins_len) - int32_t(ln) : 0;
         // the op: bases of the pool (a match segment's window bytes, an indel's insert sequence), a soft clip, or a penalty alone
@@ -1131,102 +1163,162 @@ __device__ __forceinline__ void f5_wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
+// a record as it is loaded: header + F5_SEGS path segments (five 16-byte loads) + F5_INDELS indel indices, all in flight at once
+struct F5Raw
+{
+    uint4 q0, q1, q2, q3, q4;
+    uint32_t i0, i1, i2, i3;
+};
+__device__ __forceinline__ F5Raw f5_load_raw(const PCal* src)
+{
+    F5Raw w;
+    const uint4* s4 = reinterpret_cast<const uint4*>(src);
+    w.q0 = s4[0], w.q1 = s4[1], w.q2 = s4[2], w.q3 = s4[3], w.q4 = s4[4];
+    const uint32_t* si = reinterpret_cast<const uint32_t*>(src->indels);
+    w.i0 = si[0], w.i1 = si[1], w.i2 = si[2], w.i3 = si[3];
+    return w;
+}
+
+constexpr int F5_INS_REG = 4;  // inserts of up to 64 bases each whose bytes the prologue holds in registers (a lane a base)
+
+// The prologue's global loads go out as GROUPS, each waited for once (a wave that asks for one value at a time waits ~1 us for each:
+// the prologue and the staging were 46k of a read's 122k cycles, nearly all of it such waits -- profiles/r08_f5_history.txt):
+//   group 1  what is indexed by the read alone (cal_off, status, read_off, hap_len, win_begin, n_ins, win_len): uniform loads, above
+//            the early return -- every index is in range for r < n_reads
+//   group 2  what group 1 addresses: list[] of the first round, the job's table (when it fits the copy: one copy per
+//            read, tab_lo = 0), ins_idx / ins_off, the window's codes (words of the job's code image: the pad answers for a window
+//            that leaves the reference), the read's codes and qualities, n_seg8
+//   group 3  what group 2 addresses: the first round's records (where the set's order is kept) and the inserts' bytes (up to
+//            F5_INS_REG inserts of up to 64 bases in registers, written in table order; more or longer ones: the loop)
+// With the draw from the queue that is four waits for a read of one round (counted in the assembly, profiles/r08_f5_history.txt); a
+// later round waits for its records only (its list[] entry is asked for a round ahead).  The two terms of a quality come from the
+// block's copy in LDS (q_terms: q2lncompe, then q2mis).  Not built: the read's codes and qualities as words and S.read written with
+// word stores -- they are loaded and stored a byte a lane (up to three of each in flight at once, no wait between them).
 template <int MAXR, bool TIMING>
-__device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F5Lds<MAXR>& S)
+__device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F5Lds<MAXR>& S, const double* const q_terms)
 {
     auto now = [&]() -> unsigned long long { return TIMING ? (unsigned long long)clock64() : 0ull; };
     const FlatArgs& a = fa.f;
-    const int lane = threadIdx.x & 63;
-    const int c0 = a.cal_off[r], c1 = a.cal_off[r + 1];
-    const int ncr = c1 - c0;
-    if (ncr == 0 || a.status[r] != ST_OK) return;
+    // (the lane as a value of this read's: what is computed from it -- addresses of the loads below -- is computed here, not once
+    // per kernel and kept in scratch memory, whose reload is one more wait in the middle of a group)
+    int lane_of_read = threadIdx.x & 63;
+    __asm__ volatile("" : "+v"(lane_of_read));
+    const int lane = lane_of_read;
     unsigned long long stamp[8];
-    stamp[0] = now();
+    stamp[0] = now(); // (before group 1: the prologue's figure holds every trip of the read but the draw, as it did)
     const unsigned long long wall0 = TIMING ? (unsigned long long)wall_clock64() : 0ull; // (the constant 100 MHz counter: the block's life in time)
+    // ---- group 1 (the empty statement keeps the loads together above the early return: every value is asked for before the first
+    // is looked at; they are the same in every lane)
+    int g1_c0 = a.cal_off[r], g1_c1 = a.cal_off[r + 1];
+    int32_t g1_status = a.status[r];
+    int64_t g1_ro = a.read_off[r], g1_ro1 = a.read_off[r + 1];
+    int32_t g1_P = a.hap_len[r], g1_win_begin = a.win_begin[r], g1_n_ins = a.n_ins[r], g1_win_len = a.win_len[r];
+    __asm__ volatile("" : "+v"(g1_c0), "+v"(g1_c1), "+v"(g1_status), "+v"(g1_ro), "+v"(g1_ro1), "+v"(g1_P), "+v"(g1_win_begin), "+v"(g1_n_ins), "+v"(g1_win_len));
+    auto uniform64 = [](const int64_t v) -> int64_t {
+        return int64_t(uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(uint64_t(v)))))) |
+                       (uint64_t(uint32_t(__builtin_amdgcn_readfirstlane(int(uint32_t(uint64_t(v) >> 32))))) << 32));
+    };
+    const int c0 = __builtin_amdgcn_readfirstlane(g1_c0), c1 = __builtin_amdgcn_readfirstlane(g1_c1);
+    const int32_t status_r = __builtin_amdgcn_readfirstlane(g1_status);
+    const int64_t ro = uniform64(g1_ro), ro1 = uniform64(g1_ro1);
+    const int32_t P = __builtin_amdgcn_readfirstlane(g1_P);
+    const int32_t win_begin = __builtin_amdgcn_readfirstlane(g1_win_begin);
+    const int n_ins = __builtin_amdgcn_readfirstlane(g1_n_ins);
+    const int32_t win_len = __builtin_amdgcn_readfirstlane(g1_win_len);
+    const double ln_quarter = fa.tab->ln_quarter, ln_noncand = fa.tab->ln_noncand;
+    const int ncr = c1 - c0;
+    if (ncr == 0 || status_r != ST_OK) return;
     for (int i = 1; i < 8; ++i) stamp[i] = 0;
-    const int64_t ro = a.read_off[r];
-    const int32_t L = int32_t(a.read_off[r + 1] - ro);
-    const int32_t P = a.hap_len[r];
+    const int32_t L = int32_t(ro1 - ro);
     if (L > MAXR || P > F5_MAX_POOL) {
         if (lane == 0) atomicAdd(fa.n_unhandled, 1);
         return;
     }
-    const int32_t win_begin = a.win_begin[r];
-    const int n_ins = a.n_ins[r];
+    // the job's table fits the copy: one copy per read, every index relative to entry 0
+    const int job_n_tab = a.job.n_tab;
+    const bool whole_tab = job_n_tab <= F5_TAB;
+    uint8_t* const order = S.hap + ((P + 8 + 3) & ~3);
+    const bool sorted_order = (F5_SORT != 0) && ncr > 64 && ncr <= 256 && ((P + 8 + 3) & ~3) + ncr <= int(sizeof(S.hap));
+    // ---- group 2, every load issued before the first use
+    // where the lane's record of the coming round is: list[] a round ahead (the first round's here, where the lanes take the read's
+    // alignments in the set's order, or after the sort; the next round's while this round's sums run), so that a round waits for its
+    // records only
+    int32_t slot_next = 0;
+    if (!sorted_order && lane < ncr) slot_next = a.list[c0 + lane];
+    int32_t lst[4]; // (a read whose alignments are put in order first: list[] of all of them)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        lst[k] = 0;
+        if (sorted_order && lane + 64 * k < ncr) lst[k] = a.list[c0 + lane + 64 * k];
+    }
+    F5Tab g; // lane t: entry t of the job's table (whole_tab)
+    g.pos = 0, g.del = 0, g.ins_len = 0, g.type_cand = 0, g.ins_at = -1;
+    uint32_t g_ins_off = 0;
+    if (whole_tab && lane < job_n_tab) {
+        const PIndel& e = a.job.tab[lane];
+        g.pos = e.pos;
+        g.del = e.del;
+        g.ins_len = e.ins_len;
+        g.type_cand = unsigned(e.type) | (unsigned(e.cand) << 8);
+        g_ins_off = e.ins_off;
+    }
     int my_ins_idx = -1;    // lane k < n_ins: the table index of the read's insert k and where its sequence starts in the pool
     int32_t my_ins_off = 0;
-    // ---- the pool's bytes (as pool_fill_kernel), the read, its rows of terms, the pool's layout
+    if (lane < n_ins) {
+        my_ins_idx = a.ins_idx[size_t(r) * INS_CAP + lane];
+        my_ins_off = a.ins_off[size_t(r) * INS_CAP + lane];
+    }
+    // the window's codes, a lane a word of the pool: bytes [win_len, P + 8) stay SK_BAM_ANY
+    constexpr int HAP_WORDS = int(sizeof(S.hap)) / 4, HAP_K = (HAP_WORDS + 63) / 64;
+    constexpr uint32_t ANY4 = 0x01010101u * uint32_t(SK_BAM_ANY);
+    uint32_t hw[HAP_K];
     {
-        const int16_t* idx = a.ins_idx + size_t(r) * INS_CAP;
-        const int32_t* off = a.ins_off + size_t(r) * INS_CAP;
-        // (insert k's length and source stay in lane k's registers -- the fill below takes them by readlane; its table index and
-        // offset go into the round's table copy, F5Tab::ins_at)
-        int32_t my_ins_len = 0;
-        uint32_t my_ins_src = 0;
-        if (lane < n_ins) {
-            const int t_idx = idx[lane];
-            my_ins_idx = t_idx;
-            my_ins_off = off[lane];
-            my_ins_len = int32_t(a.job.tab[t_idx].ins_len);
-            my_ins_src = a.job.tab[t_idx].ins_off;
-        }
-        const int32_t win_len = a.win_len[r];
-        // (the window's bytes first: they do not depend on the insert table just written)
-        for (int32_t i = lane; i < P + 8; i += 64) {
-            uint8_t v = SK_BAM_ANY;
-            if (i < win_len) {
-                const int32_t p = win_begin + i; // reference_contig_segment::get_base :46-51
-                const bool outside = (p < a.ref_offset || p >= a.ref_offset + a.ref_len);
-                if (outside && a.ref_outside) atomicAdd(a.ref_outside, 1);
-                v = outside ? uint8_t(SK_BAM_ANY) : code_of(a.ref[p - a.ref_offset]);
-            }
-            S.hap[i] = v;
-        }
-        f5_wave_sync();
-        for (int k = 0; k < n_ins; ++k) { // the insert sequences, in table order (a later one overwrites an earlier one, as pool_fill_kernel)
-            const int32_t o = __builtin_amdgcn_readlane(my_ins_off, k), n = __builtin_amdgcn_readlane(my_ins_len, k);
-            const uint32_t src = uint32_t(__builtin_amdgcn_readlane(int(my_ins_src), k));
-            for (int32_t i = lane; i < n; i += 64)
-                if (o + i < P) S.hap[o + i] = code_of(a.ins_pool[src + uint32_t(i)]);
-        }
-        const SkTables* __restrict__ T = fa.tab;
-        for (int32_t i = lane; i < L + 12; i += 64) {
-            unsigned q = 0;
-            uint8_t code = SK_BAM_ANY;
-            if (i < L) {
-                code = a.read_code[ro + i];
-                q = fa.read_qual[ro + i];
-                if (q > 70u) { // the reference throws (qscore_cache.cpp:53-75): flagged, sk_check_device_errors reports it
-                    atomicOr(fa.err, unsigned(SK_DEVERR_QSCORE));
-                    q = 70u;
-                }
-            }
-            S.read[i] = code & 15u;
-            if (i < L + 8) { // (the row of a '=' base adds its agree term either way, an N base and a pad row +0.0)
-                const unsigned c = code & 15u;
-                const bool adds = i < L && c != 15u;
-                const double agree = adds ? T->q2lncompe[q] : 0.0;
-                S.row[F5_ROW * i] = agree;
-                S.row[F5_ROW * i + 1] = 0.0;
-                S.row[F5_ROW * i + 2] = !adds ? 0.0 : (c == 0u) ? agree : T->q2mis[q];
+        // (32-bit from here: a window that begins further out than the pad reads pad all the same)
+        const int32_t p_max = int32_t(min(int64_t(a.ref_len) + F5_CODE_PAD - 4, int64_t(INT_MAX - 2 * F5_CODE_PAD)));
+        const int32_t wbase = int32_t(min(max(int64_t(win_begin) - int64_t(a.ref_offset), int64_t(-2 * F5_CODE_PAD)), int64_t(p_max) + F5_CODE_PAD));
+#pragma unroll
+        for (int k = 0; k < HAP_K; ++k) {
+            const int w = lane + 64 * k;
+            hw[k] = ANY4;
+            if (4 * w < win_len) {
+                // (a word that lies beyond the pad on either side holds positions outside the reference only, as the pad does)
+                const int32_t p = min(max(wbase + 4 * w, -F5_CODE_PAD), p_max);
+                uint32_t v;
+                __builtin_memcpy(&v, a.ref_code + p, 4);
+                hw[k] = v;
             }
         }
     }
-    const double ln_quarter = fa.tab->ln_quarter, ln_noncand = fa.tab->ln_noncand;
-
+    constexpr int READ_K = (MAXR + 12 + 63) / 64;
+    uint8_t rc[READ_K], rq[READ_K];
+#pragma unroll
+    for (int k = 0; k < READ_K; ++k) {
+        const int i = lane + 64 * k;
+        rc[k] = SK_BAM_ANY;
+        rq[k] = 0;
+        if (i < L) {
+            rc[k] = a.read_code[ro + i];
+            rq[k] = fa.read_qual[ro + i];
+        }
+    }
+    uint8_t seg8[4]; // (left by pool_bounds_kernel, which reads every record anyway; looked at after the pool is placed)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        seg8[k] = 0;
+        if (sorted_order && lane + 64 * k < ncr) seg8[k] = a.n_seg8[c0 + lane + 64 * k];
+    }
     // The read's candidate alignments in order of path length, longest first (a counting sort over the segment counts, the order in the
     // unused tail of the pool's bytes): a wave's walk lasts as long as its longest path, so a round of like paths wastes fewer turns
     // and the last, partly filled round gets the short ones.  Reads with more than 256 candidate alignments keep the set's order.
-    uint8_t* const order = S.hap + ((P + 8 + 3) & ~3);
-    const bool sorted_order = (F5_SORT != 0) && ncr > 64 && ncr <= 256 && ((P + 8 + 3) & ~3) + ncr <= int(sizeof(S.hap));
+    // Done before the pool is placed: the order lies past the pool's bytes, and the first round's records can go out at once.  list[] of
+    // all the read's alignments, up to 256, is parked in the slots meanwhile (the first round's walk is the first to write there).
     if (sorted_order) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (lane + 64 * k < ncr) S.slot[lane + 64 * k] = uint32_t(lst[k]);
         int seg_of[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int j = lane + 64 * k;
-            seg_of[k] = (j < ncr) ? int(a.n_seg8[c0 + j]) : -1; // (left by pool_bounds_kernel, which reads every record anyway)
-            seg_of[k] = min(seg_of[k], F5_SEGS + 1);
-        }
+        for (int k = 0; k < 4; ++k) seg_of[k] = (lane + 64 * k < ncr) ? min(int(seg8[k]), F5_SEGS + 1) : -1;
         // (only the segment counts that occur: a read's alignments have a handful of distinct ones -- the loop over all eighteen was ~650
         // of a read's ~7 800 instructions)
         unsigned present = 0;
@@ -1244,6 +1336,103 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
                 const uint64_t m = __ballot(seg_of[k] == v);
                 if (seg_of[k] == v) order[at + __popcll(m & ((1ull << lane) - 1ull))] = uint8_t(lane + 64 * k);
                 at += __popcll(m);
+            }
+        }
+        f5_wave_sync(); // (the order written)
+        slot_next = int32_t(S.slot[order[lane]]); // (more than 64 alignments: every lane has one)
+    }
+    // ---- group 3: the inserts' bytes, then the first round's records -- all issued before either is looked at
+    // (insert k's length and source stay in lane k's registers; its table index and offset go into the table copy, F5Tab::ins_at)
+    int32_t my_ins_len = 0;
+    uint32_t my_ins_src = 0;
+    if (whole_tab) {
+        const int32_t len_t = __shfl(int32_t(g.ins_len), my_ins_idx & 63);
+        const uint32_t src_t = uint32_t(__shfl(int(g_ins_off), my_ins_idx & 63));
+        if (lane < n_ins) {
+            my_ins_len = len_t;
+            my_ins_src = src_t;
+        }
+    } else if (lane < n_ins) {
+        my_ins_len = int32_t(a.job.tab[my_ins_idx].ins_len);
+        my_ins_src = a.job.tab[my_ins_idx].ins_off;
+    }
+    const bool ins_in_regs = n_ins <= F5_INS_REG && !__any(my_ins_len > 64);
+    uint32_t ib[F5_INS_REG]; // (a register each: bytes packed into one would be waited for one by one)
+    int32_t ib_n[F5_INS_REG];
+    uint32_t ib_src[F5_INS_REG];
+#pragma unroll
+    for (int k = 0; k < F5_INS_REG; ++k) { // (lengths and sources first: the one wait for them stands before the first insert's load)
+        ib_n[k] = ins_in_regs ? __builtin_amdgcn_readlane(my_ins_len, k) : 0; // (a lane that is no insert holds 0)
+        ib_src[k] = uint32_t(__builtin_amdgcn_readlane(int(my_ins_src), k));
+    }
+#pragma unroll
+    for (int k = 0; k < F5_INS_REG; ++k) {
+        ib[k] = SK_BAM_ANY;
+        if (lane < ib_n[k]) ib[k] = a.ins_code[ib_src[k] + uint32_t(lane)];
+    }
+    // (every lane loads -- one without an alignment the record its slot_next names, 0 or a former round's, which nothing looks at:
+    // a load that some lanes skip is merged with the registers' former values, and that merge waits for the load where it is issued)
+    F5Raw raw0 = f5_load_raw(a.pool + slot_next);
+    // ---- the pool's bytes (as pool_fill_kernel), the read, its rows of terms, the pool's layout
+    if (a.ref_outside && lane == 0) { // (the window's positions that lie outside the job's reference segment: they read as N)
+        const int64_t b = max(int64_t(win_begin), int64_t(a.ref_offset));
+        const int64_t e = min(int64_t(win_begin) + int64_t(win_len), int64_t(a.ref_offset) + int64_t(a.ref_len));
+        const int32_t outside = win_len - int32_t(max(e - b, int64_t(0)));
+        if (outside > 0) atomicAdd(a.ref_outside, outside);
+    }
+    {
+        uint32_t* const hap_w = reinterpret_cast<uint32_t*>(S.hap);
+        const int n_words = (P + 8 + 3) >> 2; // (at most HAP_WORDS - 1: the array holds F5_MAX_POOL + 12 bytes)
+#pragma unroll
+        for (int k = 0; k < HAP_K; ++k) {
+            const int w = lane + 64 * k;
+            const int keep = win_len - 4 * w; // bytes of the word that are the window's
+            const uint32_t m = (keep >= 4) ? 0xffffffffu : (keep <= 0) ? 0u : ((1u << (8 * keep)) - 1u);
+            if (w < n_words) hap_w[w] = (hw[k] & m) | (ANY4 & ~m);
+        }
+    }
+    if (whole_tab) {
+        if (lane < job_n_tab) S.tab[lane] = g;
+        f5_wave_sync();
+        // (the read's inserts are distinct table indices, pool_layout_kernel: a lane an insert, no two write the same entry)
+        if (lane < n_ins && my_ins_idx < job_n_tab) S.tab[my_ins_idx].ins_at = my_ins_off;
+    }
+    f5_wave_sync();
+    // the insert sequences, in table order (a later one overwrites an earlier one, as pool_fill_kernel)
+    if (ins_in_regs) {
+#pragma unroll
+        for (int k = 0; k < F5_INS_REG; ++k) {
+            if (k < n_ins) {
+                const int32_t o = __builtin_amdgcn_readlane(my_ins_off, k), n = __builtin_amdgcn_readlane(my_ins_len, k);
+                if (lane < n && o + lane < P) S.hap[o + lane] = uint8_t(ib[k]);
+            }
+        }
+    } else {
+        for (int k = 0; k < n_ins; ++k) {
+            const int32_t o = __builtin_amdgcn_readlane(my_ins_off, k), n = __builtin_amdgcn_readlane(my_ins_len, k);
+            const uint32_t src = uint32_t(__builtin_amdgcn_readlane(int(my_ins_src), k));
+            for (int32_t i = lane; i < n; i += 64)
+                if (o + i < P) S.hap[o + i] = a.ins_code[src + uint32_t(i)];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < READ_K; ++k) {
+        const int32_t i = lane + 64 * k;
+        if (i < L + 12) {
+            unsigned q = rq[k];
+            const uint8_t code = rc[k];
+            if (q > 70u) { // the reference throws (qscore_cache.cpp:53-75): flagged, sk_check_device_errors reports it
+                atomicOr(fa.err, unsigned(SK_DEVERR_QSCORE));
+                q = 70u;
+            }
+            S.read[i] = code & 15u;
+            if (i < L + 8) { // (the row of a '=' base adds its agree term either way, an N base and a pad row +0.0)
+                const unsigned c = code & 15u;
+                const bool adds = i < L && c != 15u;
+                const double agree = adds ? q_terms[q] : 0.0;
+                S.row[F5_ROW * i] = agree;
+                S.row[F5_ROW * i + 1] = 0.0;
+                S.row[F5_ROW * i + 2] = !adds ? 0.0 : (c == 0u) ? agree : q_terms[SK_NQ + 1 + q];
             }
         }
     }
@@ -1266,14 +1455,12 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
         rec.ind = 0;
         rec.ind_lo = 0;
         uint64_t ind_raw0 = 0, ind_raw1 = 0; // the record's eight 16-bit indel indices, until the round's table copy is placed
+        if (j0 > 0) raw0 = f5_load_raw(a.pool + slot_next);
         if (has) {
-            const PCal* src = a.pool + a.list[c0 + my_j];
-            const uint4* s4 = reinterpret_cast<const uint4*>(src);
-            const uint4 q0 = s4[0], q1 = s4[1], q2 = s4[2], q3 = s4[3], q4 = s4[4];
-            const uint32_t* si = reinterpret_cast<const uint32_t*>(src->indels);
-            const uint32_t i0 = si[0], i1 = si[1], i2 = si[2], i3 = si[3];
-            ind_raw0 = uint64_t(i0) | (uint64_t(i1) << 32);
-            ind_raw1 = uint64_t(i2) | (uint64_t(i3) << 32);
+            const F5Raw w = raw0;
+            const uint4 q0 = w.q0, q1 = w.q1, q2 = w.q2, q3 = w.q3, q4 = w.q4;
+            ind_raw0 = uint64_t(w.i0) | (uint64_t(w.i1) << 32);
+            ind_raw1 = uint64_t(w.i2) | (uint64_t(w.i3) << 32);
             rec.w0 = q0.x;
             rec.w1 = q0.y;
             rec.w2 = q0.z;
@@ -1297,7 +1484,27 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
         // the table entries this round's alignments name
         auto raw_indel = [&](const int k) -> int { return int(int16_t(((k & 4) ? ind_raw1 : ind_raw0) >> (16 * (k & 3)))); };
         int tab_lo = 0;
-        {
+        if (whole_tab) {
+            // the prologue's copy holds the job's table: tab_lo = 0, nothing to place per round
+            bool out_of_table = false;
+            if (has && fits) {
+                auto check = [&](const int i) { out_of_table = out_of_table || i < 0 || i >= job_n_tab; };
+                const int ni = rec.n_indels();
+                for (int i = 0; i < ni; ++i) check(raw_indel(i));
+                if (rec.lead() >= 0) check(rec.lead());
+                if (rec.trail() >= 0) check(rec.trail());
+            }
+            // (a record beyond the compact form, an index that is none of the table's: the staged chain takes the job)
+            if (__any((has && !fits) || out_of_table)) {
+                if (lane == 0) atomicAdd(fa.n_unhandled, 1);
+                return;
+            }
+            uint64_t ind = 0;
+#pragma unroll
+            for (int k = 0; k < F5_INDELS; ++k) ind |= uint64_t(unsigned(raw_indel(k)) & 63u) << (6 * k);
+            rec.ind = ind;
+            rec.ind_lo = 0;
+        } else {
             int lo = INT_MAX, hi = INT_MIN;
             if (has && fits) {
                 auto add = [&](const int i) {
@@ -1327,7 +1534,7 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
             for (int k = 0; k < F5_INDELS; ++k) ind |= uint64_t(unsigned(raw_indel(k) - tab_lo) & 63u) << (6 * k);
             rec.ind = ind;
             rec.ind_lo = tab_lo;
-            if (lane < n_tab) { // (n_tab <= F5_TAB <= 64: a lane an entry)
+            if (lane < n_tab) { // (n_tab <= F5_TAB <= 32: a lane an entry)
                 const PIndel& g = a.job.tab[tab_lo + lane];
                 F5Tab e;
                 e.pos = g.pos;
@@ -1348,24 +1555,34 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
         // op that covers read positions, and one for the read's end
         int n_ent = 0;
         bool bad = false;
+        bool cons_mine = false;
+        uint8_t cons_seen = 1;
         {
             const unsigned long long tA0 = now();
-            n_ent = f5_walk_selects(S, rec, has, tab_lo, win_begin, a.job.consulted, L, P, myslot);
+            uint32_t cons = 0; // the table entries whose candidate status this lane's alignment consults: bit index - tab_lo
+            n_ent = f5_walk_selects(S, rec, has, tab_lo, win_begin, cons, L, P, myslot);
             const unsigned long long tA1 = now();
             stamp[7] += tA1 - tA0; // the walk
             bad = n_ent < 0;
             if (has) {
                 // the candidate-status lookups the host form performs for every indel of the alignment (cal_to_c)
-                if (a.job.consulted) {
-                    const int ni = rec.n_indels();
-                    for (int i = 0; i < ni; ++i) a.job.consulted[rec.indel(i)] = 1;
-                    if (rec.lead() >= 0) a.job.consulted[rec.lead()] = 1;
-                    if (rec.trail() >= 0) a.job.consulted[rec.trail()] = 1;
-                }
+                const int ni = rec.n_indels();
+                for (int i = 0; i < ni; ++i) cons |= 1u << ((rec.indel(i) - tab_lo) & 31);
+                if (rec.lead() >= 0) cons |= 1u << ((rec.lead() - tab_lo) & 31);
+                if (rec.trail() >= 0) cons |= 1u << ((rec.trail() - tab_lo) & 31);
                 if (bad) a.status[r] = ST_FAIL;
+            }
+            // the round's entries: one OR over the wave, lane t looks at entry tab_lo + t and marks it where it reads 0 (a stale 0 costs a
+            // store of the 1 that is there already) -- a byte store per lane per indel stood in front of the next round's record loads
+            if (a.job.consulted) {
+#pragma unroll
+                for (int d = 32; d > 0; d >>= 1) cons |= uint32_t(__shfl_xor(int(cons), d));
+                cons_mine = lane < 32 && ((cons >> lane) & 1u) != 0u;
+                if (cons_mine) cons_seen = a.job.consulted[tab_lo + lane];
             }
             (void)tA1;
         }
+        if (j0 + 64 + lane < ncr) slot_next = a.list[c0 + (sorted_order ? int(order[j0 + 64 + lane]) : j0 + 64 + lane)];
         __builtin_amdgcn_wave_barrier();
         const unsigned long long td = now();
         stamp[4] += td - tc; // phase A
@@ -1374,6 +1591,10 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
             const double lnp = f5_sum(S, myslot, n_ent, ln_noncand, ln_quarter);
             fa.scores[c0 + my_j] = lnp;
         }
+        if (cons_mine && cons_seen == 0) a.job.consulted[tab_lo + lane] = 1;
+        // (the record's registers are the next round's to load: nothing of them lives through the walk and the sums)
+        raw0.q0 = raw0.q1 = raw0.q2 = raw0.q3 = raw0.q4 = make_uint4(0, 0, 0, 0);
+        raw0.i0 = raw0.i1 = raw0.i2 = raw0.i3 = 0;
         stamp[5] += now() - td; // phase B
     }
     if (fa.dbg && lane == 0) {
@@ -1399,13 +1620,17 @@ template <int MAXR, bool TIMING, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 4))) void flatten_score_kernel(const FusedScoreArgs fa, const int n_reads)
 {
     __shared__ __attribute__((aligned(16))) F5Lds<MAXR> S[WAVES];
+    // the two terms of every quality, once per block (every wave reaches the barrier: it stands before the first draw)
+    __shared__ double q_terms[F5_Q_TERMS];
+    for (int i = threadIdx.x; i < F5_Q_TERMS; i += 64 * WAVES) q_terms[i] = (i <= SK_NQ) ? fa.tab->q2lncompe[i] : fa.tab->q2mis[i - (SK_NQ + 1)];
+    __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     for (;;) {
         int r = 0;
         if (lane == 0) r = int(atomicAdd(&fa.queue[0], 1u));
         r = __builtin_amdgcn_readfirstlane(r);
         if (r >= n_reads) break;
-        f5_read<MAXR, TIMING>(fa, r, S[wave]);
+        f5_read<MAXR, TIMING>(fa, r, S[wave], q_terms);
         f5_wave_sync(); // (the wave's LDS object is the next read's)
     }
     if (lane == 0) {
@@ -1977,7 +2202,7 @@ struct EnumBuffers
 {
     DevBuf in_arena, zero_arena, minmax_arena, mask_arena;
     HostBuf h_in_arena, h_zero_arena;
-    View tab, ins, toggle, ref, reads, read_off, read_code, read_qual, r2i, i2r, orig, map_level;
+    View tab, ins, toggle, ref, ref_code, ins_code, reads, read_off, read_code, read_qual, r2i, i2r, orig, map_level;
     View counters, status, warn, n_raw, hap_len, fill, n_uniq, consulted;
     View win_begin, ins_lo, win_end, ins_hi, evmask, addmask;
     View h_counters, h_status, h_warn, h_n_raw, h_hap_len, h_n_uniq, h_consulted;
@@ -2173,6 +2398,9 @@ static int enum_device_run_impl(const SkEnumInput* in, SkEnumOutput* out, const 
         { &B.i2r, in->i2r, with_stage3 ? 8 * size_t(in->n_tab) : 0, 0 },
         { &B.orig, in->orig, with_stage3 ? 4 * size_t(in->n_tab) : 0, 0 },
         { &B.map_level, in->map_level, with_stage3 ? 4 * size_t(n) : 0, 0 },
+        // (no source: the code images are written into the mirror below)
+        { &B.ref_code, nullptr, size_t(std::max(in->ref_len, 0)) + 2 * size_t(F5_CODE_PAD), 0 },
+        { &B.ins_code, nullptr, size_t(in->ins_pool_len), 0 },
     };
     const int n_ins_p = int(sizeof(ins_p) / sizeof(ins_p[0]));
     const size_t in_bytes = lay_out(ins_p, n_ins_p);
@@ -2199,7 +2427,17 @@ static int enum_device_run_impl(const SkEnumInput* in, SkEnumOutput* out, const 
     HRES(h_zero_arena, zero_bytes);
     for (int i = 0; i < n_ins_p; ++i) {
         ins_p[i].view->p = static_cast<char*>(B.in_arena.p) + ins_p[i].off;
-        if (ins_p[i].bytes) std::memcpy(static_cast<char*>(B.h_in_arena.p) + ins_p[i].off, ins_p[i].src, ins_p[i].bytes);
+        if (ins_p[i].bytes && ins_p[i].src) std::memcpy(static_cast<char*>(B.h_in_arena.p) + ins_p[i].off, ins_p[i].src, ins_p[i].bytes);
+    }
+    { // the job's code images, made once where its reference and its insert pool go up
+        const CodeLut& lut = code_lut();
+        const size_t ref_n = size_t(std::max(in->ref_len, 0));
+        uint8_t* rc = static_cast<uint8_t*>(B.h_in_arena.p) + size_t(static_cast<char*>(B.ref_code.p) - static_cast<char*>(B.in_arena.p));
+        std::memset(rc, SK_BAM_ANY, size_t(F5_CODE_PAD));
+        for (size_t i = 0; i < ref_n; ++i) rc[size_t(F5_CODE_PAD) + i] = lut.code[uint8_t(in->ref[i])];
+        std::memset(rc + size_t(F5_CODE_PAD) + ref_n, SK_BAM_ANY, size_t(F5_CODE_PAD));
+        uint8_t* ic = static_cast<uint8_t*>(B.h_in_arena.p) + size_t(static_cast<char*>(B.ins_code.p) - static_cast<char*>(B.in_arena.p));
+        for (size_t i = 0; i < size_t(in->ins_pool_len); ++i) ic[i] = lut.code[uint8_t(in->ins_pool[i])];
     }
     for (int i = 0; i < n_zero_p; ++i) {
         zero_p[i].view->p = static_cast<char*>(B.zero_arena.p) + zero_p[i].off;
@@ -2387,6 +2625,8 @@ static int enum_device_run_impl(const SkEnumInput* in, SkEnumOutput* out, const 
         fa.job = dj;
         fa.ins_pool = B.ins.as<char>();
         fa.ref = B.ref.as<char>();
+        fa.ref_code = B.ref_code.as<uint8_t>() + F5_CODE_PAD;
+        fa.ins_code = B.ins_code.as<uint8_t>();
         fa.ref_offset = in->ref_offset;
         fa.ref_len = in->ref_len;
         fa.n_reads = n;
@@ -2632,6 +2872,8 @@ static int enum_device_run_impl(const SkEnumInput* in, SkEnumOutput* out, const 
     fa.job = dj;
     fa.ins_pool = B.ins.as<char>();
     fa.ref = B.ref.as<char>();
+    fa.ref_code = B.ref_code.as<uint8_t>() + F5_CODE_PAD;
+    fa.ins_code = B.ins_code.as<uint8_t>();
     fa.ref_offset = in->ref_offset;
     fa.ref_len = in->ref_len;
     fa.n_reads = n;
