@@ -1282,6 +1282,95 @@ int sk_active_regions_dev(int32_t win_begin, int32_t n_pos, const sk_intake_site
                           sk_active_region* dev_regions, int64_t region_cap, int32_t* dev_n_regions, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Region haplotypes: what the detector keeps per read for haplotype generation, and what the reference
+ * does with it first -- read segments, haplotype generation by counting, haplotype selection -- for every region of the list
+ * sk_active_regions[_dev] leaves.
+ *
+ *   the store    ActiveRegionReadBuffer::insertMatch / insertMismatch / insertSoftClipSegment / insertIndel
+ *                (L/starling_common/ActiveRegionReadBuffer.cpp:26-141) as addAlignmentIndelsToPosProcessor calls them
+ *                (L/starling_common/starling_pos_processor_indel_util.cpp:428-481, via starling_pos_processor_base.cpp:447-450), in
+ *                closed form: a read that is not low-MAPQ registers MATCH or MISMATCH(base) at every base of a match segment, DELETE
+ *                at every position of a primitive deletion observation (SK_INDEL_INDEL, deletion_length > 0, ins_len == 0; noise
+ *                included), INSERT -- over a mismatch MISMATCH_INSERT -- at key.pos - 1 of a primitive insertion observation, and
+ *                SOFT_CLIP at pos - 1 (leading) or after the last aligned base (trailing).  Swaps, breakpoints, edge indels and hard
+ *                clips register nothing: a hole.
+ *   the string   getHaplotypeBase (:143-171): MATCH the reference base (N outside the segment), INSERT the reference base and the
+ *                insert, MISMATCH_INSERT the read base and the insert, DELETE nothing.
+ *   per region   processHaplotypes' range and size check (L/starling_common/ActiveRegionProcessor.cpp:45-56,
+ *                MaxRefSpanToBypassAssembly = 250); getReadSegments with includePartialReads = false, minReadSegmentLength = 1
+ *                (ActiveRegionReadBuffer.cpp:191-256); generateHaplotypesWithCounting (ActiveRegionProcessor.cpp:79-114,
+ *                MinFracReadsCoveringRegion = 0.65f, compared in float); selectHaplotypes and selectOrDropHaplotypesWithSameCount
+ *                (:416-516, MinHaplotypeCount = 3; equal counts keep std::map<std::string> order, as libstdc++'s insertion sort of
+ *                up to 16 elements does); isFilterSecondHaplotypeAsSequencerPhasingNoise with doHaplotypesMeetPhasingErrorCondition1
+ *                (:296-414).
+ *
+ * A read's index in the call is its align id.  The reference keeps the store under (id % 1000, pos % 1000) and never clears it;
+ * where two (read, position) pairs of one region's reads could share a slot, or where more than 16 haplotypes reach
+ * MinHaplotypeCount (std::sort's introsort then decides the order among equal counts), the region is SK_HAP_DECLINED with a reason,
+ * never answered wrongly.
+ *
+ * On one stream sk_read_intake_dev -> sk_ref_anchors_dev -> sk_active_regions_dev -> sk_region_haplotypes_dev run with no host copy
+ * in between.  Out of scope: routing the results into the caller; the assembly fallback (generateHaplotypesWithAssembly,
+ * getReadSegments with partial reads) -- a region whose counting fails reports its status and the host does the rest;
+ * doNotUseHaplotyping's IndelBuffer marks; _haplotypesToExclude; the multi-sample synchroniser; external and forced candidates;
+ * chaining into sk_global_align_dev without a host copy (its sizes are host arguments: query_off / the sequence pool are laid out
+ * as its query_off / query, so one small copy of totals suffices).
+ * ---------------------------------------------------------------------------------------------------------------- */
+enum { SK_HAP_COUNTED = 0, SK_HAP_BYPASSED, SK_HAP_NO_READS, SK_HAP_TOO_FEW_COVERING, SK_HAP_DECLINED };
+enum {
+    SK_HAP_DECLINE_NONE = 0,
+    SK_HAP_DECLINE_GROUPS,            /* more than SK_HAP_MAX_GROUPS haplotypes reach MinHaplotypeCount */
+    SK_HAP_DECLINE_READ_INDEX_SPREAD, /* the reads registered in the region lie 1 000 or more indices apart (_variantInfo[id % 1000]) */
+    SK_HAP_DECLINE_READ_SPAN          /* a registered read's first and last position lie 1 000 or more apart ([pos % 1000]) */
+};
+#define SK_HAP_MAX_SELECTED 3 /* ploidy + 1 */
+#define SK_HAP_MAX_GROUPS 16
+#define SK_HAP_MAX_REF_SPAN 250
+typedef struct sk_selected_haplotype { /* _selectedHaplotypes[k], _selectedAlignIdLists[k] */
+    int64_t seq_off;     /* its bytes: seq_pool[seq_off .. seq_off + seq_len) */
+    int64_t support_off; /* its reads, ascending indices: support_pool[support_off .. support_off + count) */
+    uint32_t seq_len, count;
+    uint32_t is_reference; /* equals the region's reference segment (_refSegment) */
+    uint32_t pad;
+} sk_selected_haplotype;
+typedef struct sk_region_haplotypes_rec {
+    int32_t status, reason;                    /* SK_HAP_*, SK_HAP_DECLINE_* */
+    uint32_t n_reads_aligned, n_reads_covering; /* numReadsAlignedToActiveRegion, readSegmentsForHaplotypeGeneration.size() */
+    uint32_t n_selected, pad;
+    sk_selected_haplotype hap[SK_HAP_MAX_SELECTED];
+} sk_region_haplotypes_rec;
+/** Room for the selected haplotypes' bytes of n_regions regions: SK_HAP_MAX_SELECTED * SK_PILEUP_MAX_READ_LEN each (a haplotype is
+ *  never longer than its read's bases).  Host arithmetic only (works without a device); -1 for a negative count. */
+int64_t sk_region_haplotypes_seq_bound(int64_t n_regions);
+/** Room for the selected haplotypes' supporting reads: min(n_reads, 1000) per region (a read supports one haplotype of a region, and
+ *  a region whose reads lie further apart is declined).  Host arithmetic only; -1 for a negative count. */
+int64_t sk_region_haplotypes_support_bound(int32_t n_reads, int64_t n_regions);
+/** Bytes of device scratch sk_region_haplotypes_dev needs.  Host arithmetic only. */
+size_t sk_region_haplotypes_scratch_bytes(int32_t n_reads, int64_t region_cap, int64_t seq_cap, int64_t support_cap);
+/** The reads as sk_read_intake takes them, obs_off / obs as it leaves them, is_fwd_strand[n_reads] (alignment::is_fwd_strand),
+ *  [buf_begin, buf_end) the read buffer's range (_readBufferRange), ploidy 1 or 2, regions[n_regions] as sk_active_regions leaves
+ *  them (made_at is not read).  recs[n_regions]; the selected haplotypes' bytes lie back to back in region order in seq_pool, their
+ *  k-th at query_off[k] .. query_off[k + 1] (query_off[3 * n_regions + 1], the first totals[0] + 1 entries written); totals[3]: the
+ *  number of selected haplotypes, their bytes, their supporting reads.  Refused with a message: what sk_read_intake refuses, a region
+ *  with end <= begin, a ploidy other than 1 or 2, seq_cap / support_cap below the bounds, negative sizes. */
+int sk_region_haplotypes(const char* ref_seq, int32_t ref_offset, int32_t ref_len, int32_t n_reads, const int64_t* read_off, const uint8_t* read_code,
+                         const int64_t* path_off, const int32_t* n_seg, const sk_path_seg* path, const int32_t* pos, const uint8_t* low_mapq,
+                         const uint8_t* is_fwd_strand, const int64_t* obs_off, const sk_intake_obs* obs, uint32_t max_indel_size, int32_t buf_begin,
+                         int32_t buf_end, int32_t ploidy, const sk_active_region* regions, int32_t n_regions, sk_region_haplotypes_rec* recs,
+                         uint8_t* seq_pool, int64_t seq_cap, int32_t* support_pool, int64_t support_cap, int64_t* query_off, int64_t* totals);
+/** The same on device memory, dev_regions / dev_n_regions included (region_cap: the room of dev_regions, dev_recs and, times
+ *  SK_HAP_MAX_SELECTED plus one, of dev_query_off); only enqueues.  seq_cap / support_cap must reach the bounds of region_cap.  Input
+ *  the host entry refuses raises the sticky device flag instead (sk_check_device_errors); such a region's record is SK_HAP_BYPASSED
+ *  with nothing selected. */
+int sk_region_haplotypes_dev(const char* dev_ref_seq, int32_t ref_offset, int32_t ref_len, int32_t n_reads, const int64_t* dev_read_off,
+                             const uint8_t* dev_read_code, const int64_t* dev_path_off, const int32_t* dev_n_seg, const sk_path_seg* dev_path,
+                             const int32_t* dev_pos, const uint8_t* dev_low_mapq, const uint8_t* dev_is_fwd_strand, const int64_t* dev_obs_off,
+                             const sk_intake_obs* dev_obs, uint32_t max_indel_size, int32_t buf_begin, int32_t buf_end, int32_t ploidy,
+                             const sk_active_region* dev_regions, const int32_t* dev_n_regions, int64_t region_cap, sk_region_haplotypes_rec* dev_recs,
+                             uint8_t* dev_seq_pool, int64_t seq_cap, int32_t* dev_support_pool, int64_t support_cap, int64_t* dev_query_off,
+                             int64_t* dev_totals, void* dev_scratch, size_t scratch_bytes, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * SURVEY.md section 8f rank 4, the output side: the non-variant blocks of the gVCF.
  *
  * gvcf_writer::queue_site_record (L/applications/starling/gvcf_writer.cpp:278-302) asks, site after site and per sample, whether the

@@ -29,6 +29,7 @@ HIP_SOURCES = [
     "csrc/bgzf_deflate.hip",
     "csrc/read_intake.hip",
     "csrc/active_region_detect.hip",
+    "csrc/region_haplotypes.hip",
     "csrc/gvcf_block.hip",
 ]
 HOST_SOURCES = [

@@ -234,6 +234,7 @@ EXPORTS = [
     "sk_bgzf_scan", "sk_bgzf_inflate", "sk_bgzf_inflate_prefixed", "sk_bgzf_inflate_dev", "sk_bgzf_deflate_bound", "sk_bgzf_deflate", "sk_bgzf_deflate_dev", "sk_bam_header_end", "sk_bam_scan_records", "sk_bam_decode", "sk_bam_decode_kept", "sk_bam_decode_dev", "sk_normalize_alignments", "sk_normalize_alignments_dev",
     "sk_intake_options_default", "sk_read_intake_obs_bound", "sk_read_intake", "sk_read_intake_dev", "sk_read_intake_scratch_bytes",
     "sk_ar_state_initial", "sk_ref_anchors", "sk_ref_anchors_dev", "sk_active_regions_bound", "sk_active_regions", "sk_active_regions_dev",
+    "sk_region_haplotypes_seq_bound", "sk_region_haplotypes_support_bound", "sk_region_haplotypes_scratch_bytes", "sk_region_haplotypes", "sk_region_haplotypes_dev",
     "sk_align_builder_create", "sk_align_builder_destroy", "sk_align_builder_clear", "sk_align_builder_append", "sk_align_builder_add_read",
     "sk_align_builder_finish", "sk_align_builder_error", "sk_align_builder_set_host_threads",
     "sk_align_scores_default", "sk_global_align",
@@ -353,6 +354,16 @@ def lib():
         L.sk_ref_anchors_dev.argtypes = L.sk_ref_anchors.argtypes + [c_void_p]
         L.sk_active_regions.argtypes = [C.c_int32, C.c_int32] + [c_void_p] * 6 + [C.c_int64, c_void_p]
         L.sk_active_regions_dev.argtypes = L.sk_active_regions.argtypes + [c_void_p]
+        L.sk_region_haplotypes_seq_bound.restype = C.c_int64
+        L.sk_region_haplotypes_seq_bound.argtypes = [C.c_int64]
+        L.sk_region_haplotypes_support_bound.restype = C.c_int64
+        L.sk_region_haplotypes_support_bound.argtypes = [C.c_int32, C.c_int64]
+        L.sk_region_haplotypes_scratch_bytes.restype = C.c_size_t
+        L.sk_region_haplotypes_scratch_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int64, C.c_int64]
+        L.sk_region_haplotypes.argtypes = [c_void_p, C.c_int32, C.c_int32, C.c_int32] + [c_void_p] * 10 + [C.c_uint32, C.c_int32, C.c_int32, C.c_int32, c_void_p, C.c_int32,
+                                           c_void_p, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, c_void_p]
+        L.sk_region_haplotypes_dev.argtypes = [c_void_p, C.c_int32, C.c_int32, C.c_int32] + [c_void_p] * 10 + [C.c_uint32, C.c_int32, C.c_int32, C.c_int32, c_void_p, c_void_p,
+                                               C.c_int64, c_void_p, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, c_void_p, c_void_p, C.c_size_t, c_void_p]
         L.sk_align_colmat_words.restype = C.c_int64
         L.sk_align_colmat_words.argtypes = [c_void_p]
         L.sk_align_prepare_cols.argtypes = [c_void_p] * 4
@@ -1527,6 +1538,74 @@ def active_regions(win_begin, sites, is_candidate, is_anchor, state=None, region
     _check(lib().sk_active_regions(int(win_begin), n, _p(sites) if n else None, _p(cand) if n else None, _p(anchor) if n else None, _p(state_in), _p(state_out),
                                    _p(regions), cap, _p(n_regions)))
     return regions[:int(n_regions[0])], state_out
+
+
+HAP_COUNTED, HAP_BYPASSED, HAP_NO_READS, HAP_TOO_FEW_COVERING, HAP_DECLINED = range(5)
+HAP_DECLINE_NONE, HAP_DECLINE_GROUPS, HAP_DECLINE_READ_INDEX_SPREAD, HAP_DECLINE_READ_SPAN = range(4)
+HAP_MAX_SELECTED = 3
+SELECTED_HAPLOTYPE_DTYPE = np.dtype([("seq_off", "<i8"), ("support_off", "<i8"), ("seq_len", "<u4"), ("count", "<u4"), ("is_reference", "<u4"), ("pad", "<u4")])
+REGION_HAPLOTYPES_DTYPE = np.dtype([("status", "<i4"), ("reason", "<i4"), ("n_reads_aligned", "<u4"), ("n_reads_covering", "<u4"), ("n_selected", "<u4"), ("pad", "<u4"),
+                                    ("hap", SELECTED_HAPLOTYPE_DTYPE, (HAP_MAX_SELECTED,))])
+assert SELECTED_HAPLOTYPE_DTYPE.itemsize == 32 and REGION_HAPLOTYPES_DTYPE.itemsize == 120
+
+
+def region_haplotypes_bounds(n_reads, n_regions):
+    """room for the selected haplotypes' bytes and supporting reads of n_regions regions; host arithmetic, works without a device"""
+    L = lib()
+    return int(L.sk_region_haplotypes_seq_bound(int(n_regions))), int(L.sk_region_haplotypes_support_bound(int(n_reads), int(n_regions)))
+
+
+def region_haplotype_records(recs, seq_pool, support_pool):
+    """REGION_HAPLOTYPES_DTYPE[] and the two pools -> [dict(status, reason, n_reads_aligned, n_reads_covering, haps [dict(seq, count,
+    is_reference, support)])]: the records with the haplotype strings and support lists looked up"""
+    out = []
+    for r in recs:
+        haps = []
+        for k in range(int(r["n_selected"])):
+            h = r["hap"][k]
+            so, sl, po, pc = int(h["seq_off"]), int(h["seq_len"]), int(h["support_off"]), int(h["count"])
+            haps.append(dict(seq=bytes(seq_pool[so:so + sl]).decode("latin-1"), count=pc, is_reference=int(h["is_reference"]),
+                             support=[int(x) for x in support_pool[po:po + pc]]))
+        out.append(dict(status=int(r["status"]), reason=int(r["reason"]), n_reads_aligned=int(r["n_reads_aligned"]),
+                        n_reads_covering=int(r["n_reads_covering"]), haps=haps))
+    return out
+
+
+def region_haplotypes(ref_seq, ref_offset, reads, low_mapq, is_fwd_strand, regions, buf_begin, buf_end, ploidy=2, intake=None, opt=None, raw=False):
+    """reads: the form read_intake takes; regions: ACTIVE_REGION_DTYPE[] or [(begin, end)]; intake: read_intake's result for these reads
+    (computed here when None) -> per-region records with haplotype strings and support lists (region_haplotype_records) through
+    sk_region_haplotypes; raw=True: dict(recs, seq_pool, support_pool, query_off, totals) as the entry point leaves them"""
+    L = lib()
+    n = len(reads)
+    opt = opt or intake_options()
+    if intake is None:
+        intake = read_intake(ref_seq, ref_offset, reads, low_mapq, 0, 0, opt)
+    read_off, code, path_off, n_seg, path, pos = pack_reads(reads)
+    low = np.zeros(n + 1, np.uint8)
+    low[:n] = np.asarray(low_mapq, np.uint8)[:n] != 0
+    fwd = np.zeros(n + 1, np.uint8)
+    fwd[:n] = np.asarray(is_fwd_strand, np.uint8)[:n] != 0
+    obs_off = np.ascontiguousarray(intake["obs_off"], np.int64)
+    obs = np.ascontiguousarray(intake["obs"], INTAKE_OBS_DTYPE)
+    if isinstance(regions, np.ndarray) and regions.dtype == ACTIVE_REGION_DTYPE:
+        reg = np.ascontiguousarray(regions)
+    else:
+        reg = np.zeros(len(regions), ACTIVE_REGION_DTYPE)
+        for i, r in enumerate(regions):
+            reg[i] = (int(r[0]), int(r[1]), 0)
+    m = len(reg)
+    seq_cap, support_cap = region_haplotypes_bounds(n, m)
+    recs = np.zeros(max(m, 1), REGION_HAPLOTYPES_DTYPE)
+    seq_pool = np.zeros(max(seq_cap, 1), np.uint8)
+    support_pool = np.zeros(max(support_cap, 1), np.int32)
+    query_off = np.zeros(HAP_MAX_SELECTED * m + 1, np.int64)
+    totals = np.zeros(3, np.int64)
+    ref_b = ref_seq.encode() if isinstance(ref_seq, str) else bytes(ref_seq)
+    _check(L.sk_region_haplotypes(ref_b, int(ref_offset), len(ref_b), n, _p(read_off), _p(code), _p(path_off), _p(n_seg), _p(path), _p(pos), _p(low), _p(fwd),
+                                  _p(obs_off), _p(obs) if len(obs) else None, int(opt.max_indel_size), int(buf_begin), int(buf_end), int(ploidy),
+                                  _p(reg) if m else None, m, _p(recs), _p(seq_pool), seq_cap, _p(support_pool), support_cap, _p(query_off), _p(totals)))
+    res = dict(recs=recs[:m], seq_pool=seq_pool[:int(totals[1])], support_pool=support_pool[:int(totals[2])], query_off=query_off[:int(totals[0]) + 1], totals=totals)
+    return res if raw else region_haplotype_records(res["recs"], res["seq_pool"], res["support_pool"])
 
 
 BAI_CHUNK_DTYPE = np.dtype([("begin", "<u8"), ("end", "<u8")])

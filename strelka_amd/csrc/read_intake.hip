@@ -610,6 +610,8 @@ enum { IB_REF = 0, IB_READ_OFF, IB_CODE, IB_PATH_OFF, IB_NSEG, IB_PATH, IB_POS, 
 
 } // namespace
 
+const char* sk_intake_path_issue(const sk_path_seg* path, const int n_seg, const int64_t read_len) { return intake_path_issue(path, n_seg, read_len); }
+
 extern "C" {
 
 void sk_intake_options_default(sk_intake_options* o)

@@ -64,10 +64,13 @@ struct SkContext
 enum {
     SK_DEVERR_QSCORE = 1u, // a basecall quality above 70 reached a scoring kernel (qscore_cache.cpp:53-75 throws)
     SK_DEVERR_INTAKE = 2u, // sk_read_intake_dev met a read or path its host entry refuses, or ran out of obs_cap
-    SK_DEVERR_ACTIVE_REGION = 4u // sk_active_regions_dev: createActiveRegion's assertion failed; sk_ref_anchors_dev: a span_pos before m
+    SK_DEVERR_ACTIVE_REGION = 4u, // sk_active_regions_dev: createActiveRegion's assertion failed; sk_ref_anchors_dev: a span_pos before m
+    SK_DEVERR_HAPLOTYPES = 8u // sk_region_haplotypes_dev met a read or a region its host entry refuses, or ran out of a pool
 };
 
 SkContext& sk_ctx();
+// what sk_read_intake refuses of a read's path (read_intake.hip; nullptr: addAlignmentIndelsToPosProcessor takes it)
+const char* sk_intake_path_issue(const sk_path_seg* path, int n_seg, int64_t read_len);
 void sk_set_error(const std::string& msg);
 int sk_fail(const std::string& msg);
 

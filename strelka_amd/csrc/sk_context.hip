@@ -404,6 +404,8 @@ int sk_check_device_errors(void)
         return sk_fail("sk_read_intake_dev: a read longer than SK_PILEUP_MAX_READ_LEN, a path whose read length is not the read_off span, or obs_cap too small");
     if (flags & SK_DEVERR_ACTIVE_REGION)
         return sk_fail("sk_active_regions_dev: a region's start is not before its end anchor (createActiveRegion's assertion) or region_cap too small, or sk_ref_anchors_dev: a span_pos before the finder's first position");
+    if (flags & SK_DEVERR_HAPLOTYPES)
+        return sk_fail("sk_region_haplotypes_dev: a read longer than SK_PILEUP_MAX_READ_LEN or with descending offsets, an empty region, or a pool too small");
     return sk_fail("strelka_amd: a kernel reported an error");
 }
 
