@@ -100,6 +100,10 @@ int sk_check_device_errors(void);
  *  the host libm (csrc/germline_common.h, v0r0), its pending terms and all of variant 0's from the device routines; on a host whose
  *  libm is not the restated one (STRELKA_AMD_ALLOW_INEXACT_LIBM) the two agree to the documented 1e-5, not bit for bit. */
 int sk_debug_set_g3_variant(int variant);
+/** Test hook: how many loci the last sk_site_digt_call_fused (the host-buffer entry point) left to the global-memory pass -- those
+ *  deeper than the packed sort key's call index allows, needing more ranked calls or term slots than the LDS path holds, or whose
+ *  group would take std::sort's heap-sort fallback.  The kernels' own work counter, copied back with the results. */
+int sk_debug_g3_global_pass_count(void);
 /** Test hook: on != 0 makes every kernel take the path it takes on a host whose libm is NOT the restated one (the device
  *  math library's double routines stand in; sk_libm_restated() then reports 0); on == 0 restores the sk_init outcome.
  *  Lets the test suite measure the documented 1e-5 bar of that path on a box where the exact path is available. */

@@ -12,6 +12,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ORACLE_SO = os.path.join(HERE, "libstrelka_oracle.so")
+PROBE_SO = os.path.join(HERE, "libsort_probe.so")
 REF_SO = os.path.join(HERE, "_ref", "libstrelka_ref.so")
 vp = C.c_void_p
 
@@ -89,8 +90,58 @@ def oracle():
         L.sko_error_prob_to_qphred.argtypes = [C.c_double]
         L.sko_ln_error_prob_to_qphred_f.argtypes = [C.c_float]
         L.sko_germline_lnpriors.argtypes = [C.c_double, vp]
+        L.sko_heap_sort_runs.restype = C.c_ulong
+        L.sko_heap_sort_runs_reset.restype = None
         _oracle = L
     return _oracle
+
+
+def sort_idx_by_key_desc(key):
+    """the order the restated std::sort (sko_sort_idx_by_key_desc) leaves 0..n-1 in, comparator key[a] > key[b]"""
+    key = np.ascontiguousarray(key, np.uint16)
+    idx = np.arange(len(key), dtype=np.uint32)
+    oracle().sko_sort_idx_by_key_desc(_p(idx), len(key), _p(key if len(key) else np.zeros(1, np.uint16)))
+    return idx
+
+
+def heap_sort_runs():
+    """how often the restated std::sort took its heap-sort fallback since heap_sort_runs_reset()"""
+    return int(oracle().sko_heap_sort_runs())
+
+
+def heap_sort_runs_reset():
+    oracle().sko_heap_sort_runs_reset()
+
+
+_probe = None
+
+
+def sort_probe():
+    """oracle/libsort_probe.so: the C++ library's own std::sort and the adversary for it; None when it has not been built"""
+    global _probe
+    if _probe is None and os.path.exists(PROBE_SO):
+        L = C.CDLL(PROBE_SO)
+        L.skp_std_sort_idx_by_key_desc.restype = None
+        L.skp_sort_adversary.restype = None
+        _probe = L
+    return _probe
+
+
+def std_sort_idx_by_key_desc(key):
+    """the order the genuine std::sort leaves 0..n-1 in, comparator key[a] > key[b]"""
+    key = np.ascontiguousarray(key, np.uint16)
+    idx = np.arange(len(key), dtype=np.uint32)
+    sort_probe().skp_std_sort_idx_by_key_desc(_p(idx), len(key), _p(key if len(key) else np.zeros(1, np.uint16)))
+    return idx
+
+
+def sort_adversary_keys(n, k=1, mirror=False, base=3):
+    """keys of n calls that drive std::sort(comparator key[a] > key[b]) into lopsided partitions: the adversary's values (a permutation
+    of 0..n-1, oracle/sort_probe.cpp) coarsened by the divisor k into ceil(n / k) distinct keys from `base` up"""
+    val = np.zeros(max(n, 1), np.int32)
+    sort_probe().skp_sort_adversary(n, 1 if mirror else 0, _p(val))
+    val = val[:n].astype(np.int64)
+    return (base + (val if mirror else (n - 1 - val)) // k).astype(np.uint16)
 
 
 def ref_available():

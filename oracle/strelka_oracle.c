@@ -165,8 +165,14 @@ static void s_adjust_heap(uint32_t* first, long hole, long len, uint32_t value, 
     s_push_heap(first, hole, top, value, key);
 }
 
+/* how often the depth-limit fallback ran (a test counter: tests that mean to drive the heap sort ask whether they did) */
+static unsigned long g_heap_sort_runs;
+unsigned long sko_heap_sort_runs(void) { return g_heap_sort_runs; }
+void sko_heap_sort_runs_reset(void) { g_heap_sort_runs = 0; }
+
 static void s_heap_sort(uint32_t* first, uint32_t* last, const uint16_t* key)
 {
+    ++g_heap_sort_runs;
     /* __partial_sort(first,last,last) = __heap_select (make_heap only, as middle==last) + __sort_heap */
     const long len = last - first;
     if (len >= 2) {

@@ -30,6 +30,9 @@ float sko_log_sum2f(float a, float b);
 /* ---- libstdc++ std::sort restated (introsort + final insertion sort), descending-q comparator of
  *      L/blt_common/adjust_joint_eprob.cpp:41-53.  idx[n] is permuted in place; key[] is indexed by idx values. */
 void sko_sort_idx_by_key_desc(uint32_t* idx, int n, const uint16_t* key);
+/* test counter: runs of the heap-sort fallback (introsort's depth limit exhausted) since the last reset, whoever called the sort */
+unsigned long sko_heap_sort_runs(void);
+void sko_heap_sort_runs_reset(void);
 
 /* ---- hot path A: scoreCandidateAlignment (L/starling_common/starling_read_align_score.cpp:261-499) ---- */
 enum { SKO_NONE = 0, SKO_MATCH, SKO_INSERT, SKO_DELETE, SKO_SKIP, SKO_SOFT_CLIP, SKO_HARD_CLIP, SKO_PAD, SKO_SEQ_MATCH,

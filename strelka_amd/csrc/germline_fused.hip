@@ -935,6 +935,7 @@ int sk_upload_pileup_internal(const sk_pileup_batch* hb, bool need_de, SkArena& 
                               sk_pileup_batch& d, hipStream_t st, int64_t& total_calls);
 
 static int g_g3_variant_override = -1;
+static uint32_t g_g3_global_pass_count = 0; // work_count of the last sk_site_digt_call_fused, copied back with its results
 
 extern "C" {
 
@@ -943,6 +944,8 @@ int sk_debug_set_g3_variant(int variant)
     g_g3_variant_override = variant;
     return 0;
 }
+
+int sk_debug_g3_global_pass_count(void) { return int(g_g3_global_pass_count); }
 
 int sk_site_digt_call_fused_dev(const sk_pileup_batch* b, const sk_germline_options* opt, sk_digt_call* dev_out,
                                 float* dev_de_tmp, int want_de, void* dev_scratch, int64_t n_calls, void* hip_stream)
@@ -997,6 +1000,7 @@ int sk_site_digt_call_fused(const sk_pileup_batch* hb, const sk_germline_options
     if (sk_site_digt_call_fused_dev(&d, opt, dout, dde, out_de ? 1 : 0, scratch, total, ctx.stream)) return 1;
     SK_HIP(skrt::memcpyAsync(out, dout, sizeof(sk_digt_call) * hb->n_loci, hipMemcpyDeviceToHost, ctx.stream));
     if (out_de && total) SK_HIP(skrt::memcpyAsync(out_de, dde, 4 * total, hipMemcpyDeviceToHost, ctx.stream));
+    SK_HIP(skrt::memcpyAsync(&g_g3_global_pass_count, scratch + total, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx.stream)); // (work_count)
     SK_HIP(skrt::streamSynchronize(ctx.stream));
     return 0;
 }
