@@ -108,6 +108,11 @@ int sk_debug_g3_global_pass_count(void);
  *  math library's double routines stand in; sk_libm_restated() then reports 0); on == 0 restores the sk_init outcome.
  *  Lets the test suite measure the documented 1e-5 bar of that path on a box where the exact path is available. */
 int sk_debug_force_device_libm(int on);
+/** Test hook for the two decline rules of sk_region_alleles[_dev] that no input reaches: no_edge_deletion != 0 drops the required edge
+ *  deletion from the detector's alignment scores, so that the aligner's beginPos may exceed 0 (SK_ALLELE_DECLINE_BEGIN_POS);
+ *  ids_twice != 0 makes the kernel add a repeated key's haplotype id twice, so that a key both alternates carry adds up to more than 3
+ *  (SK_ALLELE_DECLINE_ID_SUM).  Both 0 (the state of a fresh process) is the reference's behaviour; nothing else sets them. */
+void sk_debug_region_alleles(int no_edge_deletion, int ids_twice);
 
 /** Host copies of the q-score tables the kernels use (71 entries each, Q0..Q70; L/blt_util/qscore_cache.hh:66-68). */
 int sk_get_qscore_tables(double* q2p, double* q2lncompe, double* q2lne);
@@ -1316,9 +1321,9 @@ int sk_active_regions_dev(int32_t win_begin, int32_t n_pos, const sk_intake_site
  * On one stream sk_read_intake_dev -> sk_ref_anchors_dev -> sk_active_regions_dev -> sk_region_haplotypes_dev run with no host copy
  * in between.  Out of scope: routing the results into the caller; the assembly fallback (generateHaplotypesWithAssembly,
  * getReadSegments with partial reads) -- a region whose counting fails reports its status and the host does the rest;
- * doNotUseHaplotyping's IndelBuffer marks; _haplotypesToExclude; the multi-sample synchroniser; external and forced candidates;
- * chaining into sk_global_align_dev without a host copy (its sizes are host arguments: query_off / the sequence pool are laid out
- * as its query_off / query, so one small copy of totals suffices).
+ * doNotUseHaplotyping's IndelBuffer marks; _haplotypesToExclude; the multi-sample synchroniser; external and forced candidates.
+ * What a region does with its selected haplotypes -- the aligner, the walk, the records for the buffers -- is sk_region_alleles[_dev]
+ * (below), chained on the same stream without a host copy.
  * ---------------------------------------------------------------------------------------------------------------- */
 enum { SK_HAP_COUNTED = 0, SK_HAP_BYPASSED, SK_HAP_NO_READS, SK_HAP_TOO_FEW_COVERING, SK_HAP_DECLINED };
 enum {
@@ -1373,6 +1378,103 @@ int sk_region_haplotypes_dev(const char* dev_ref_seq, int32_t ref_offset, int32_
                              const sk_active_region* dev_regions, const int32_t* dev_n_regions, int64_t region_cap, sk_region_haplotypes_rec* dev_recs,
                              uint8_t* dev_seq_pool, int64_t seq_cap, int32_t* dev_support_pool, int64_t support_cap, int64_t* dev_query_off,
                              int64_t* dev_totals, void* dev_scratch, size_t scratch_bytes, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Region alleles: what an active region does to the rest of the program once its haplotypes are
+ * selected -- ActiveRegionProcessor::processSelectedHaplotypes (L/starling_common/ActiveRegionProcessor.cpp:518-571),
+ * discoverIndelsAndMismatches (:573-707) and processDiscoveredIndelsAndMismatches (:709-757) -- for every region of the list, from
+ * what sk_region_haplotypes[_dev] leaves.  Single sample: _synchronizedActiveRegion is the region.
+ *
+ *   prev_end     _prevActiveRegionEnd: prev_end_in for region 0, regions[i - 1].end afterwards (ActiveRegionDetector.cpp:248: it
+ *                advances whatever became of the region before).
+ *   alternates   the selected haplotypes with is_reference == 0, in selection order: at most two
+ *                (selectOrDropHaplotypesWithSameCount, :486-516); haplotype_id 1 and 2 (:562-570).
+ *   alignment    each alternate against _refSegment (the reference over [begin, end), 'N' outside the segment) with the detector's
+ *                scores (sk_align_scores_default), by the GlobalAligner kernel (:591).
+ *   the walk     :593-706: MISMATCH keys at positions >= prev_end; insertions and deletions left-shifted against get_base, dropped
+ *                when longer than max_indel_size, shifted below prev_end, at or past end, or next to an 'N'; numIndels.
+ *   the rule     :553-560: doNotAddMismatchesToIndelBuffer when no alternate has an indel or the alternates' distinct MISMATCH keys
+ *                number more than MaxNumMismatchesToAddToIndelBuffer = 10 (ActiveRegionProcessor.hh).
+ *   the records  one per (alternate, key), alternate by alternate, path order inside: what a router replays as addCandidateSnv
+ *                (:725-728, every MISMATCH record) and, where to_indel_buffer is set, addIndelObservation for every read of
+ *                hap[hap_slot]'s support list (:733-740) with haplotypeId += haplotype_id and altAlleleHaplotypeCountRatio += ratio
+ *                (:750-755); ratio = count / float(n_reads_aligned), one float division (:719).
+ *
+ * Declined, never guessed (SK_HAP_DECLINED with an SK_ALLELE_DECLINE_* reason, no alleles): the aligner's beginPos > 0 (the
+ * reference asserts, :596-599); a left shift the reference's loop would not end (an all-N indel left of an all-N reference); a
+ * key whose haplotype ids add up to more than 3 (the assertion at :752); a selected haplotype longer than max_hap_len.
+ * A region whose haplotype record is not SK_HAP_COUNTED, or that selected nothing, passes its status and reason through with no
+ * alleles: doNotUseHaplotyping's marks and the assembly fallback stay the host's.
+ *
+ * On one stream sk_read_intake_dev -> sk_ref_anchors_dev -> sk_active_regions_dev -> sk_region_haplotypes_dev ->
+ * sk_region_alleles_dev run with no host copy in between.  Not routed into adapter/ yet.  Out of scope: routing;
+ * addIndelObservation / addCandidateSnv themselves; the assembly fallback; doNotUseHaplotyping's marks; _haplotypesToExclude and the
+ * somatic branch; the multi-sample synchroniser; filterOutConflictingForcedIndels.
+ * ---------------------------------------------------------------------------------------------------------------- */
+enum {
+    SK_ALLELE_DECLINE_BEGIN_POS = 4, /* (after SK_HAP_DECLINE_*) the aligner's beginPos > 0 */
+    SK_ALLELE_DECLINE_LEFT_SHIFT,    /* a left shift the reference's loop would not end */
+    SK_ALLELE_DECLINE_ID_SUM,        /* a key's haplotype ids add up to more than 3 */
+    SK_ALLELE_DECLINE_HAP_LEN        /* a selected alternate haplotype longer than max_hap_len */
+};
+#define SK_ALLELE_MAX_ALT 2
+#define SK_ALLELE_MAX_MISMATCHES 10 /* MaxNumMismatchesToAddToIndelBuffer */
+typedef struct sk_region_allele { /* one discovered IndelKey of one alternate haplotype */
+    int32_t pos, type;        /* key.pos; SK_INDEL_INDEL or SK_INDEL_MISMATCH */
+    uint32_t del_len, ins_len; /* key.deletionLength; key.insertSequence is insert_pool[ins_off .. ins_off + ins_len) */
+    int64_t ins_off;
+    int32_t hap_slot;         /* the k of the haplotype record's hap[k] it came from: hence its support list */
+    int32_t haplotype_id;     /* 1 for the region's first alternate, 2 for its second */
+    float ratio;              /* altHaplotypeCountRatio (:719) */
+    int32_t to_indel_buffer;  /* 0 for a MISMATCH key under doNotAddMismatchesToIndelBuffer (:731) */
+    int32_t same_as;          /* the region's first earlier record (its index within the region) with an equal key (IndelKey::operator==), or -1 */
+    int32_t id_sum;           /* same_as == -1 and to_indel_buffer: what IndelSampleData::haplotypeId ends as for a key the buffer did not hold (:750) */
+    float ratio_sum;          /* ... and altAlleleHaplotypeCountRatio: 0.0f plus the ratios in record order (:755); 0 otherwise */
+    int32_t pad;
+} sk_region_allele;
+typedef struct sk_region_alleles_rec {
+    int32_t status, reason; /* SK_HAP_*; SK_HAP_DECLINE_* passed through or SK_ALLELE_DECLINE_* */
+    int32_t prev_end;       /* the _prevActiveRegionEnd used */
+    uint32_t n_alt;         /* alternates aligned */
+    uint32_t n_alleles;     /* records: alleles[allele_off .. allele_off + n_alleles) */
+    uint32_t n_indels;      /* numIndels, added over the alternates: isAnyIndel is n_indels != 0 */
+    uint32_t n_distinct_mismatches; /* mismatchSet.size() (:554) */
+    uint32_t do_not_add_mismatches; /* doNotAddMismatchesToIndelBuffer */
+    int64_t allele_off, insert_off; /* the region's records and insert bytes (n_insert_bytes of them) */
+    uint32_t n_insert_bytes, pad;
+    int32_t score[SK_ALLELE_MAX_ALT];    /* the aligner's score per alternate */
+    int32_t hap_slot[SK_ALLELE_MAX_ALT]; /* the alternates' slots in the haplotype record */
+} sk_region_alleles_rec;
+/** Room for the records of n_regions regions: 2 * (SK_HAP_MAX_REF_SPAN + max_hap_len) each -- a key takes at least one reference
+ *  position of the region or one haplotype byte of its own.  Host arithmetic only (works without a device); -1 for a negative count
+ *  or a max_hap_len outside 1..1024. */
+int64_t sk_region_alleles_allele_bound(int64_t n_regions, int32_t max_hap_len);
+/** Room for their insert bytes: 2 * max_hap_len per region (a key's bytes are the haplotype's own, or replace as many of them). */
+int64_t sk_region_alleles_insert_bound(int64_t n_regions, int32_t max_hap_len);
+/** Bytes of device scratch sk_region_alleles_dev needs: the alternates' alignment problems and paths, the aligner's back-pointers in
+ *  the stride form of (max_hap_len, SK_HAP_MAX_REF_SPAN), and the records before they are placed.  Host arithmetic only; 0 for
+ *  arguments out of range. */
+size_t sk_region_alleles_scratch_bytes(int64_t region_cap, int32_t max_hap_len);
+/** regions[n_regions] as sk_active_regions leaves them (made_at is not read), hap_recs[n_regions] and seq_pool[seq_len] as
+ *  sk_region_haplotypes leaves them (the support lists are not read: a record names its list by hap_slot); max_hap_len in 1..1024.
+ *  recs[n_regions]; the records and the insert bytes lie back to back in region order; totals[2]: records, insert bytes;
+ *  *prev_end_out: the _prevActiveRegionEnd after the last region.  Refused with a message: a counted region of no or more than
+ *  SK_HAP_MAX_REF_SPAN positions, a haplotype record outside seq_pool or with more than SK_HAP_MAX_SELECTED selected or more than
+ *  two alternates, allele_cap / insert_cap below the bounds, negative sizes. */
+int sk_region_alleles(const char* ref_seq, int32_t ref_offset, int32_t ref_len, const sk_active_region* regions, int32_t n_regions,
+                      const sk_region_haplotypes_rec* hap_recs, const uint8_t* seq_pool, int64_t seq_len, uint32_t max_indel_size, int32_t max_hap_len,
+                      int32_t prev_end_in, sk_region_alleles_rec* recs, sk_region_allele* alleles, int64_t allele_cap, uint8_t* insert_pool,
+                      int64_t insert_cap, int64_t* totals, int32_t* prev_end_out);
+/** The same on device memory, dev_regions / dev_n_regions / dev_prev_end_out included (region_cap: the room of dev_regions,
+ *  dev_hap_recs and dev_recs; seq_cap: the room of dev_seq_pool); only enqueues.  allele_cap / insert_cap must reach the bounds of the
+ *  regions there are (*dev_n_regions, known on the device only; the bounds of region_cap always suffice): below them the sticky device
+ *  flag is raised (sk_check_device_errors) and EVERY region's record is SK_HAP_BYPASSED with no alleles.  Other input the host entry
+ *  refuses raises the flag too; such a region's record is SK_HAP_BYPASSED with no alleles. */
+int sk_region_alleles_dev(const char* dev_ref_seq, int32_t ref_offset, int32_t ref_len, const sk_active_region* dev_regions, const int32_t* dev_n_regions,
+                          int64_t region_cap, const sk_region_haplotypes_rec* dev_hap_recs, const uint8_t* dev_seq_pool, int64_t seq_cap,
+                          uint32_t max_indel_size, int32_t max_hap_len, int32_t prev_end_in, sk_region_alleles_rec* dev_recs, sk_region_allele* dev_alleles,
+                          int64_t allele_cap, uint8_t* dev_insert_pool, int64_t insert_cap, int64_t* dev_totals, int32_t* dev_prev_end_out,
+                          void* dev_scratch, size_t scratch_bytes, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * SURVEY.md section 8f rank 4, the output side: the non-variant blocks of the gVCF.

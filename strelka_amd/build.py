@@ -30,6 +30,7 @@ HIP_SOURCES = [
     "csrc/read_intake.hip",
     "csrc/active_region_detect.hip",
     "csrc/region_haplotypes.hip",
+    "csrc/region_alleles.hip",
     "csrc/gvcf_block.hip",
 ]
 HOST_SOURCES = [

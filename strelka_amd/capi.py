@@ -235,6 +235,7 @@ EXPORTS = [
     "sk_intake_options_default", "sk_read_intake_obs_bound", "sk_read_intake", "sk_read_intake_dev", "sk_read_intake_scratch_bytes",
     "sk_ar_state_initial", "sk_ref_anchors", "sk_ref_anchors_dev", "sk_active_regions_bound", "sk_active_regions", "sk_active_regions_dev",
     "sk_region_haplotypes_seq_bound", "sk_region_haplotypes_support_bound", "sk_region_haplotypes_scratch_bytes", "sk_region_haplotypes", "sk_region_haplotypes_dev",
+    "sk_region_alleles_allele_bound", "sk_region_alleles_insert_bound", "sk_region_alleles_scratch_bytes", "sk_region_alleles", "sk_region_alleles_dev", "sk_debug_region_alleles",
     "sk_align_builder_create", "sk_align_builder_destroy", "sk_align_builder_clear", "sk_align_builder_append", "sk_align_builder_add_read",
     "sk_align_builder_finish", "sk_align_builder_error", "sk_align_builder_set_host_threads",
     "sk_align_scores_default", "sk_global_align",
@@ -364,6 +365,18 @@ def lib():
                                            c_void_p, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, c_void_p]
         L.sk_region_haplotypes_dev.argtypes = [c_void_p, C.c_int32, C.c_int32, C.c_int32] + [c_void_p] * 10 + [C.c_uint32, C.c_int32, C.c_int32, C.c_int32, c_void_p, c_void_p,
                                                C.c_int64, c_void_p, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, c_void_p, c_void_p, C.c_size_t, c_void_p]
+        L.sk_region_alleles_allele_bound.restype = C.c_int64
+        L.sk_region_alleles_allele_bound.argtypes = [C.c_int64, C.c_int32]
+        L.sk_region_alleles_insert_bound.restype = C.c_int64
+        L.sk_region_alleles_insert_bound.argtypes = [C.c_int64, C.c_int32]
+        L.sk_region_alleles_scratch_bytes.restype = C.c_size_t
+        L.sk_region_alleles_scratch_bytes.argtypes = [C.c_int64, C.c_int32]
+        L.sk_debug_region_alleles.argtypes = [C.c_int, C.c_int]
+        L.sk_debug_region_alleles.restype = None
+        L.sk_region_alleles.argtypes = [c_void_p, C.c_int32, C.c_int32, c_void_p, C.c_int32, c_void_p, c_void_p, C.c_int64, C.c_uint32, C.c_int32, C.c_int32,
+                                        c_void_p, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, c_void_p]
+        L.sk_region_alleles_dev.argtypes = [c_void_p, C.c_int32, C.c_int32, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p, C.c_int64, C.c_uint32, C.c_int32,
+                                            C.c_int32, c_void_p, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, c_void_p, c_void_p, C.c_size_t, c_void_p]
         L.sk_align_colmat_words.restype = C.c_int64
         L.sk_align_colmat_words.argtypes = [c_void_p]
         L.sk_align_prepare_cols.argtypes = [c_void_p] * 4
@@ -1606,6 +1619,85 @@ def region_haplotypes(ref_seq, ref_offset, reads, low_mapq, is_fwd_strand, regio
                                   _p(reg) if m else None, m, _p(recs), _p(seq_pool), seq_cap, _p(support_pool), support_cap, _p(query_off), _p(totals)))
     res = dict(recs=recs[:m], seq_pool=seq_pool[:int(totals[1])], support_pool=support_pool[:int(totals[2])], query_off=query_off[:int(totals[0]) + 1], totals=totals)
     return res if raw else region_haplotype_records(res["recs"], res["seq_pool"], res["support_pool"])
+
+
+ALLELE_DECLINE_BEGIN_POS, ALLELE_DECLINE_LEFT_SHIFT, ALLELE_DECLINE_ID_SUM, ALLELE_DECLINE_HAP_LEN = range(4, 8)
+ALLELE_MAX_ALT = 2
+REGION_ALLELE_DTYPE = np.dtype([("pos", "<i4"), ("type", "<i4"), ("del_len", "<u4"), ("ins_len", "<u4"), ("ins_off", "<i8"), ("hap_slot", "<i4"), ("haplotype_id", "<i4"),
+                                ("ratio", "<f4"), ("to_indel_buffer", "<i4"), ("same_as", "<i4"), ("id_sum", "<i4"), ("ratio_sum", "<f4"), ("pad", "<i4")])
+REGION_ALLELES_DTYPE = np.dtype([("status", "<i4"), ("reason", "<i4"), ("prev_end", "<i4"), ("n_alt", "<u4"), ("n_alleles", "<u4"), ("n_indels", "<u4"),
+                                 ("n_distinct_mismatches", "<u4"), ("do_not_add_mismatches", "<u4"), ("allele_off", "<i8"), ("insert_off", "<i8"),
+                                 ("n_insert_bytes", "<u4"), ("pad", "<u4"), ("score", "<i4", (ALLELE_MAX_ALT,)), ("hap_slot", "<i4", (ALLELE_MAX_ALT,))])
+assert REGION_ALLELE_DTYPE.itemsize == 56 and REGION_ALLELES_DTYPE.itemsize == 72
+
+
+class RegionAllele(C.Structure):  # sk_region_allele
+    _fields_ = [("pos", C.c_int32), ("type", C.c_int32), ("del_len", C.c_uint32), ("ins_len", C.c_uint32), ("ins_off", C.c_int64), ("hap_slot", C.c_int32),
+                ("haplotype_id", C.c_int32), ("ratio", C.c_float), ("to_indel_buffer", C.c_int32), ("same_as", C.c_int32), ("id_sum", C.c_int32),
+                ("ratio_sum", C.c_float), ("pad", C.c_int32)]
+
+
+class RegionAllelesRec(C.Structure):  # sk_region_alleles_rec
+    _fields_ = [("status", C.c_int32), ("reason", C.c_int32), ("prev_end", C.c_int32), ("n_alt", C.c_uint32), ("n_alleles", C.c_uint32), ("n_indels", C.c_uint32),
+                ("n_distinct_mismatches", C.c_uint32), ("do_not_add_mismatches", C.c_uint32), ("allele_off", C.c_int64), ("insert_off", C.c_int64),
+                ("n_insert_bytes", C.c_uint32), ("pad", C.c_uint32), ("score", C.c_int32 * ALLELE_MAX_ALT), ("hap_slot", C.c_int32 * ALLELE_MAX_ALT)]
+
+
+def region_alleles_bounds(n_regions, max_hap_len):
+    """room for the allele records and insert bytes of n_regions regions; host arithmetic, works without a device"""
+    L = lib()
+    return int(L.sk_region_alleles_allele_bound(int(n_regions), int(max_hap_len))), int(L.sk_region_alleles_insert_bound(int(n_regions), int(max_hap_len)))
+
+
+def float_bits(x):
+    return int(np.array([x], np.float32).view(np.uint32)[0])
+
+
+def region_allele_records(recs, alleles, insert_pool):
+    """REGION_ALLELES_DTYPE[], REGION_ALLELE_DTYPE[] and the insert bytes -> [dict(status, reason, prev_end, n_alt, n_indels,
+    n_distinct_mismatches, do_not_add_mismatches, score, hap_slot, alleles [dict(pos, type, del_len, ins, hap_slot, haplotype_id, ratio,
+    to_indel_buffer, same_as, id_sum, ratio_sum)])]: the records with the insert sequences looked up; floats as their bits"""
+    out = []
+    for r in recs:
+        keys = []
+        for a in alleles[int(r["allele_off"]):int(r["allele_off"]) + int(r["n_alleles"])]:
+            io, il = int(a["ins_off"]), int(a["ins_len"])
+            keys.append(dict(pos=int(a["pos"]), type=int(a["type"]), del_len=int(a["del_len"]), ins=bytes(insert_pool[io:io + il]).decode("latin-1"),
+                             hap_slot=int(a["hap_slot"]), haplotype_id=int(a["haplotype_id"]), ratio=float_bits(a["ratio"]), to_indel_buffer=int(a["to_indel_buffer"]),
+                             same_as=int(a["same_as"]), id_sum=int(a["id_sum"]), ratio_sum=float_bits(a["ratio_sum"])))
+        n_alt = int(r["n_alt"])
+        out.append(dict(status=int(r["status"]), reason=int(r["reason"]), prev_end=int(r["prev_end"]), n_alt=n_alt, n_indels=int(r["n_indels"]),
+                        n_distinct_mismatches=int(r["n_distinct_mismatches"]), do_not_add_mismatches=int(r["do_not_add_mismatches"]),
+                        score=[int(x) for x in r["score"][:n_alt]], hap_slot=[int(x) for x in r["hap_slot"][:n_alt]], alleles=keys))
+    return out
+
+
+def region_alleles(ref_seq, ref_offset, regions, haplotypes, max_indel_size=49, max_hap_len=1024, prev_end_in=-1, raw=False):
+    """regions: ACTIVE_REGION_DTYPE[] or [(begin, end)]; haplotypes: what region_haplotypes(..., raw=True) returned for them -> (per-region
+    records (region_allele_records), prev_end_out) through sk_region_alleles; raw=True: dict(recs, alleles, insert_pool, totals,
+    prev_end_out) as the entry point leaves them"""
+    L = lib()
+    if isinstance(regions, np.ndarray) and regions.dtype == ACTIVE_REGION_DTYPE:
+        reg = np.ascontiguousarray(regions)
+    else:
+        reg = np.zeros(len(regions), ACTIVE_REGION_DTYPE)
+        for i, r in enumerate(regions):
+            reg[i] = (int(r[0]), int(r[1]), 0)
+    m = len(reg)
+    hap = np.ascontiguousarray(haplotypes["recs"], REGION_HAPLOTYPES_DTYPE)
+    seq = np.ascontiguousarray(haplotypes["seq_pool"], np.uint8)
+    allele_cap, insert_cap = region_alleles_bounds(m, max_hap_len)
+    recs = np.zeros(max(m, 1), REGION_ALLELES_DTYPE)
+    alleles = np.zeros(max(allele_cap, 1), REGION_ALLELE_DTYPE)
+    insert_pool = np.zeros(max(insert_cap, 1), np.uint8)
+    totals = np.zeros(2, np.int64)
+    prev_end_out = np.zeros(1, np.int32)
+    ref_b = ref_seq.encode() if isinstance(ref_seq, str) else bytes(ref_seq)
+    _check(L.sk_region_alleles(ref_b, int(ref_offset), len(ref_b), _p(reg) if m else None, m, _p(hap) if m else None, _p(seq) if len(seq) else None, len(seq),
+                               int(max_indel_size), int(max_hap_len), int(prev_end_in), _p(recs), _p(alleles), allele_cap, _p(insert_pool), insert_cap,
+                               _p(totals), _p(prev_end_out)))
+    res = dict(recs=recs[:m], alleles=alleles[:int(totals[0])], insert_pool=insert_pool[:int(totals[1])], totals=totals, prev_end_out=int(prev_end_out[0]))
+    return res if raw else (region_allele_records(res["recs"], res["alleles"], res["insert_pool"]), res["prev_end_out"])
 
 
 BAI_CHUNK_DTYPE = np.dtype([("begin", "<u8"), ("end", "<u8")])

@@ -22,6 +22,7 @@
 #include "sk_common.h"
 
 #include <algorithm>
+#include <climits>
 #include <vector>
 
 namespace
@@ -47,6 +48,7 @@ struct GaArgs
     int64_t ptr_stride;
     int max_ref;           // LDS sizing: boundary rows and the reference copy
     int max_query;         // LDS sizing: last-column scores
+    const int32_t* dev_n;  // NULL, or the problem count in device memory: the grid is sized by a bound and blocks at or past *dev_n leave at once
 };
 
 __device__ __forceinline__ unsigned max3(int& mx, const int v0, const int v1, const int v2)
@@ -85,6 +87,7 @@ __global__ __launch_bounds__(WAVE) void global_align_kernel(const GaArgs a)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x;
     const int p = blockIdx.x;
+    if (a.dev_n && p >= *a.dev_n) return;
     const int64_t qo = a.b.query_off[p], ro = a.b.ref_off[p];
     const int Q = int(a.b.query_off[p + 1] - qo), R = int(a.b.ref_off[p + 1] - ro);
     const char* __restrict__ gq = a.b.query + qo;
@@ -365,6 +368,7 @@ int sk_global_align(const sk_global_align_batch* hb, const sk_align_scores* sc, 
     a.ptr_stride = 0;
     a.max_ref = maxR;
     a.max_query = maxQ;
+    a.dev_n = nullptr;
     if (ga_allow_lds(lds)) return 1;
     if (sg.upload(st)) return 1;
     SK_LAUNCH(global_align_kernel, dim3(n), dim3(WAVE), lds, st, a);
@@ -417,6 +421,7 @@ int sk_global_align_dev(const sk_global_align_batch* db, int64_t total_query_len
     a.ptr_stride = ga_ptr_stride(max_query_len, max_ref_len);
     a.max_ref = max_ref_len;
     a.max_query = max_query_len;
+    a.dev_n = nullptr;
     const int RW = max_ref_len + 1;
     const size_t lds = size_t(WIN) * WAVE + size_t((RW + 3) & ~3) + 4 * size_t(max_query_len + 1) + 2 * 12 * size_t(RW) + 16;
     if (ga_allow_lds(lds)) return 1;
@@ -426,3 +431,38 @@ int sk_global_align_dev(const sk_global_align_batch* db, int64_t total_query_len
 }
 
 } // extern "C"
+
+// The launch a device chain uses (region_alleles.hip): the problems' CSR was laid out by a kernel, so their count is known only on the
+// device.  grid: the bound the arrays were sized by; back-pointers in the stride form, sk_ga_ptr_bytes(grid, ...) bytes of them.
+size_t sk_ga_ptr_bytes(const int64_t grid, const int max_query_len, const int max_ref_len)
+{
+    return size_t(grid) * size_t(ga_ptr_stride(max_query_len, max_ref_len)) + size_t(WIN) * WAVE; // + slack: a window read may run past the end
+}
+
+int sk_ga_launch_counted(const sk_global_align_batch& dev_batch, const int32_t* dev_n, const int64_t grid, const int max_query_len, const int max_ref_len,
+                         const sk_align_scores& sc, int32_t* dev_out_score, int32_t* dev_out_begin_pos, sk_path_seg* dev_out_path, int32_t* dev_out_n_seg,
+                         sk_path_seg* dev_tmp_path, uint8_t* dev_ptr_scratch, hipStream_t st)
+{
+    if (grid <= 0) return 0;
+    if (!dev_n || max_query_len < 1 || max_ref_len < 1 || max_query_len > MAX_LEN || max_ref_len > MAX_LEN || grid > INT32_MAX)
+        return sk_fail("sk_ga_launch_counted: sizes out of range");
+    GaArgs a;
+    a.b = dev_batch;
+    a.sc = sc;
+    a.out_score = dev_out_score;
+    a.out_begin = dev_out_begin_pos;
+    a.out_path = dev_out_path;
+    a.out_nseg = dev_out_n_seg;
+    a.tmp_path = dev_tmp_path;
+    a.ptr_scratch = dev_ptr_scratch;
+    a.ptr_off = nullptr;
+    a.ptr_stride = ga_ptr_stride(max_query_len, max_ref_len);
+    a.max_ref = max_ref_len;
+    a.max_query = max_query_len;
+    a.dev_n = dev_n;
+    const int RW = max_ref_len + 1;
+    const size_t lds = size_t(WIN) * WAVE + size_t((RW + 3) & ~3) + 4 * size_t(max_query_len + 1) + 2 * 12 * size_t(RW) + 16;
+    if (ga_allow_lds(lds)) return 1;
+    SK_LAUNCH(global_align_kernel, dim3(unsigned(grid)), dim3(WAVE), lds, st, a);
+    return 0;
+}

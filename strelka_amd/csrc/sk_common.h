@@ -65,12 +65,18 @@ enum {
     SK_DEVERR_QSCORE = 1u, // a basecall quality above 70 reached a scoring kernel (qscore_cache.cpp:53-75 throws)
     SK_DEVERR_INTAKE = 2u, // sk_read_intake_dev met a read or path its host entry refuses, or ran out of obs_cap
     SK_DEVERR_ACTIVE_REGION = 4u, // sk_active_regions_dev: createActiveRegion's assertion failed; sk_ref_anchors_dev: a span_pos before m
-    SK_DEVERR_HAPLOTYPES = 8u // sk_region_haplotypes_dev met a read or a region its host entry refuses, or ran out of a pool
+    SK_DEVERR_HAPLOTYPES = 8u, // sk_region_haplotypes_dev met a read or a region its host entry refuses, or ran out of a pool
+    SK_DEVERR_ALLELES = 16u // sk_region_alleles_dev met a haplotype record its host entry refuses, or a capacity below its bound
 };
 
 SkContext& sk_ctx();
 // what sk_read_intake refuses of a read's path (read_intake.hip; nullptr: addAlignmentIndelsToPosProcessor takes it)
 const char* sk_intake_path_issue(const sk_path_seg* path, int n_seg, int64_t read_len);
+// D1 over problems whose count lies in device memory (global_align.hip): what a device chain launches; only enqueues
+size_t sk_ga_ptr_bytes(int64_t grid, int max_query_len, int max_ref_len);
+int sk_ga_launch_counted(const sk_global_align_batch& dev_batch, const int32_t* dev_n, int64_t grid, int max_query_len, int max_ref_len, const sk_align_scores& sc,
+                         int32_t* dev_out_score, int32_t* dev_out_begin_pos, sk_path_seg* dev_out_path, int32_t* dev_out_n_seg, sk_path_seg* dev_tmp_path,
+                         uint8_t* dev_ptr_scratch, hipStream_t st);
 void sk_set_error(const std::string& msg);
 int sk_fail(const std::string& msg);
 

@@ -406,6 +406,8 @@ int sk_check_device_errors(void)
         return sk_fail("sk_active_regions_dev: a region's start is not before its end anchor (createActiveRegion's assertion) or region_cap too small, or sk_ref_anchors_dev: a span_pos before the finder's first position");
     if (flags & SK_DEVERR_HAPLOTYPES)
         return sk_fail("sk_region_haplotypes_dev: a read longer than SK_PILEUP_MAX_READ_LEN or with descending offsets, an empty region, or a pool too small");
+    if (flags & SK_DEVERR_ALLELES)
+        return sk_fail("sk_region_alleles_dev: a haplotype record outside the sequence pool or with more than two alternates, a counted region of no or more than 250 positions, or a capacity below its bound");
     return sk_fail("strelka_amd: a kernel reported an error");
 }
 
