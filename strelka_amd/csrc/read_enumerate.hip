@@ -851,7 +851,7 @@ struct FusedScoreArgs
     unsigned* err;         // SkContext::dev_error_flags (a quality above 70)
     int32_t* n_unhandled;  // reads left to the staged kernels
     int32_t write_cals;    // the records' copy in set order (stage 3 and sk_enum_device_fetch_cals read it)
-    unsigned long long* dbg; // diagnostics ($SK_F5_TIMING): per block 8 cycle stamps, or null
+    unsigned long long* dbg; // diagnostics ($SK_F5_TIMING): per read F5_STAMPS cycle stamps, or null
     unsigned* queue;       // [2] the launch's read queue: next read, waves that have left (both 0 between launches: the last wave out zeroes them)
 };
 
@@ -862,6 +862,7 @@ struct FusedScoreArgs
 // goes from 17.8 KB to under 10 KB and a CU holds 16 of them instead of 9 (profiles/r04_a5_history.txt: a wave alone on a CU takes as
 // long as nine sharing it; with sixteen the vector unit is ~85 % busy, profiles/r05_f5_history.txt).
 constexpr int F5_SEGS = 16, F5_INDELS = 8;
+constexpr int F5_STAMPS = 9; // $SK_F5_TIMING: a read's stamps (f5_read; the ninth is the cycles of the draw that handed it out)
 constexpr int F5_SLOT = (F5_SEGS + 1) | 1; // (odd stride: conflict-free)
 __device__ __forceinline__ int f5_ent_word(const int k) { return k; }
 // doubles per read position: agree, 0.0, differ -- the read's own cases folded in (a '=' base: differ = agree; an N base and the pad
@@ -1195,7 +1196,8 @@ constexpr int F5_INS_REG = 4;  // inserts of up to 64 bases each whose bytes the
 // block's copy in LDS (q_terms: q2lncompe, then q2mis).  Not built: the read's codes and qualities as words and S.read written with
 // word stores -- they are loaded and stored a byte a lane (up to three of each in flight at once, no wait between them).
 template <int MAXR, bool TIMING>
-__device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F5Lds<MAXR>& S, const double* const q_terms)
+__device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F5Lds<MAXR>& S, const double* const q_terms,
+                                        const unsigned long long draw_cycles)
 {
     auto now = [&]() -> unsigned long long { return TIMING ? (unsigned long long)clock64() : 0ull; };
     const FlatArgs& a = fa.f;
@@ -1204,7 +1206,7 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
     int lane_of_read = threadIdx.x & 63;
     __asm__ volatile("" : "+v"(lane_of_read));
     const int lane = lane_of_read;
-    unsigned long long stamp[8];
+    unsigned long long stamp[F5_STAMPS];
     stamp[0] = now(); // (before group 1: the prologue's figure holds every trip of the read but the draw, as it did)
     const unsigned long long wall0 = TIMING ? (unsigned long long)wall_clock64() : 0ull; // (the constant 100 MHz counter: the block's life in time)
     // ---- group 1 (the empty statement keeps the loads together above the early return: every value is asked for before the first
@@ -1228,7 +1230,7 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
     const double ln_quarter = fa.tab->ln_quarter, ln_noncand = fa.tab->ln_noncand;
     const int ncr = c1 - c0;
     if (ncr == 0 || status_r != ST_OK) return;
-    for (int i = 1; i < 8; ++i) stamp[i] = 0;
+    for (int i = 1; i < F5_STAMPS; ++i) stamp[i] = 0;
     const int32_t L = int32_t(ro1 - ro);
     if (L > MAXR || P > F5_MAX_POOL) {
         if (lane == 0) atomicAdd(fa.n_unhandled, 1);
@@ -1597,10 +1599,12 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
         raw0.i0 = raw0.i1 = raw0.i2 = raw0.i3 = 0;
         stamp[5] += now() - td; // phase B
     }
-    if (fa.dbg && lane == 0) {
+    if (TIMING && fa.dbg && lane == 0) { // (the build without the stamps has no store of them either)
         stamp[6] = now();
         stamp[3] = TIMING ? (unsigned long long)wall_clock64() - wall0 : 0ull;
-        for (int i = 0; i < 8; ++i) fa.dbg[size_t(r) * 8 + i] = stamp[i];
+        stamp[8] = draw_cycles; // the draw that handed this read out, from before the atomic to its value in a scalar register (0: the
+                                // wave's first read, which is not drawn)
+        for (int i = 0; i < F5_STAMPS; ++i) fa.dbg[size_t(r) * F5_STAMPS + i] = stamp[i];
     }
 }
 
@@ -1614,8 +1618,13 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
 // same binding, only longer.  The queue's order is the job's: taking the heavy reads first, or the light ones last (lists by rounds of 64
 // candidate alignments, filled by pool_layout_kernel), was tried against the launch's tail and is SLOWER (1.33-1.37 ms: reads of one kind
 // side by side keep their waves in step -- all in their prologues, all in their walks -- where the job's own order mixes them;
-// profiles/r06_f5_history.txt).  The last wave to leave puts the queue back to zero, so that the next launch -- the same buffers, the same
-// stream -- finds it as this one did.
+// profiles/r06_f5_history.txt).  A wave's FIRST read is not drawn: wave g of the grid takes read g, and a draw hands out
+// gridDim.x * WAVES + the counter's value.  All the grid's waves used to make their first draw on the one word within the ~15 us it takes
+// to place the blocks, and a head word answers ~88 such atomics per us: the last of that burst waited ~45 us for its first read
+// (1.025 -> 0.981 ms, profiles/r09_f5_history.txt; a later draw costs a wave 3 700 - 4 600 cycles at this load, the `draw` figure of
+// $SK_F5_TIMING).  A wave whose number is past the last read leaves without a draw.  The last wave to leave puts the queue back to zero
+// -- every wave counts itself out after its last draw, whether it drew or not -- so that the next launch, the same buffers, the same
+// stream, finds it as this one did.
 template <int MAXR, bool TIMING, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 4))) void flatten_score_kernel(const FusedScoreArgs fa, const int n_reads)
 {
@@ -1625,13 +1634,19 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 4
     for (int i = threadIdx.x; i < F5_Q_TERMS; i += 64 * WAVES) q_terms[i] = (i <= SK_NQ) ? fa.tab->q2lncompe[i] : fa.tab->q2mis[i - (SK_NQ + 1)];
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (;;) {
-        int r = 0;
-        if (lane == 0) r = int(atomicAdd(&fa.queue[0], 1u));
-        r = __builtin_amdgcn_readfirstlane(r);
-        if (r >= n_reads) break;
-        f5_read<MAXR, TIMING>(fa, r, S[wave], q_terms);
+    const unsigned n_waves = gridDim.x * unsigned(WAVES);
+    unsigned r = blockIdx.x * unsigned(WAVES) + unsigned(wave); // the first read: the wave's own number, no draw
+    unsigned long long draw_cycles = 0;
+    while (r < unsigned(n_reads)) {
+        f5_read<MAXR, TIMING>(fa, int(r), S[wave], q_terms, draw_cycles);
         f5_wave_sync(); // (the wave's LDS object is the next read's)
+        const unsigned long long t0 = TIMING ? (unsigned long long)clock64() : 0ull;
+        unsigned d = 0;
+        if (lane == 0) d = atomicAdd(&fa.queue[0], 1u);
+        int drawn = __builtin_amdgcn_readfirstlane(int(d));
+        if (TIMING) __asm__ volatile("" : "+s"(drawn)); // (the second stamp stands after the value has arrived)
+        r = n_waves + unsigned(drawn);
+        draw_cycles = TIMING ? (unsigned long long)clock64() - t0 : 0ull;
     }
     if (lane == 0) {
         __threadfence();
@@ -3216,7 +3231,7 @@ extern "C" int sk_enum_device_rescore(const int32_t reps, float* out_ms, int32_t
     SK_HIP(hipEventRecord(e0, st));
     if (g_last.fused && std::getenv("SK_F5_TIMING")) { // diagnostics: where a wave of F5 spends its cycles
         FusedScoreArgs fs = g_last.fs;
-        const size_t nb = size_t(g_last.n) * 8;
+        const size_t nb = size_t(g_last.n) * F5_STAMPS;
         unsigned long long* d = nullptr;
         SK_HIP(skrt::malloc_(reinterpret_cast<void**>(&d), nb * 8));
         SK_HIP(skrt::memsetAsync(d, 0, nb * 8, st));
@@ -3226,11 +3241,11 @@ extern "C" int sk_enum_device_rescore(const int32_t reps, float* out_ms, int32_t
         SK_HIP(skrt::memcpyAsync(h.data(), d, nb * 8, hipMemcpyDeviceToHost, st));
         SK_HIP(skrt::streamSynchronize(st));
         (void)skrt::free_(d);
-        double sum[8] = { 0 };
+        double sum[F5_STAMPS] = { 0 };
         unsigned long long first = ~0ull, last = 0;
-        int nblk = 0;
+        int nblk = 0, ndrawn = 0;
         for (int r = 0; r < g_last.n; ++r) {
-            const unsigned long long* s = &h[size_t(r) * 8];
+            const unsigned long long* s = &h[size_t(r) * F5_STAMPS];
             if (s[6] == 0) continue;
             ++nblk;
             first = std::min(first, s[0]);
@@ -3239,6 +3254,8 @@ extern "C" int sk_enum_device_rescore(const int32_t reps, float* out_ms, int32_t
             for (int i = 2; i <= 5; ++i) sum[i] += double(s[i]);
             sum[7] += double(s[7]);
             sum[6] += double(s[6] - s[0]);
+            sum[8] += double(s[8]);
+            ndrawn += s[8] != 0;
         }
         for (const int grid : { 64, 256, 512, 1024, 1792, 2048, 4096 }) { // how the kernel's time grows with the blocks in flight
             if (grid > g_last.n) break;
@@ -3258,8 +3275,8 @@ extern "C" int sk_enum_device_rescore(const int32_t reps, float* out_ms, int32_t
             (void)hipEventDestroy(a1);
         }
         if (nblk)
-            std::fprintf(stderr, "[f5-timing] blocks %d: cycles per block: prologue %.0f staging %.0f phaseA %.0f (walk %.0f) phaseB %.0f total %.0f = %.1f us by the 100 MHz counter (%.0f MHz); kernel span %llu cycles => %.1f blocks in flight\n",
-                         nblk, sum[0] / nblk, sum[2] / nblk, sum[4] / nblk, sum[7] / nblk, sum[5] / nblk, sum[6] / nblk, sum[3] / nblk / 100.0,
+            std::fprintf(stderr, "[f5-timing] blocks %d: cycles per block: draw %.0f (%d drawn: %.0f each) prologue %.0f staging %.0f phaseA %.0f (walk %.0f) phaseB %.0f total %.0f = %.1f us by the 100 MHz counter (%.0f MHz); kernel span %llu cycles => %.1f blocks in flight\n",
+                         nblk, sum[8] / nblk, ndrawn, sum[8] / std::max(1, ndrawn), sum[0] / nblk, sum[2] / nblk, sum[4] / nblk, sum[7] / nblk, sum[5] / nblk, sum[6] / nblk, sum[3] / nblk / 100.0,
                          sum[6] / std::max(1.0, sum[3]) * 100.0, last - first,
                          sum[6] / double(last - first));
     }
