@@ -310,6 +310,16 @@ __global__ __launch_bounds__(256) void rank_kernel(const SetArgs a)
 enum { DYN_N_GROUPED = 0, DYN_N_CALS, DYN_N_LIGHT, DYN_N_HEAVY, DYN_FLAGS, DYN_MAX_CALS, DYN_REF_OUTSIDE, DYN_COUNT = 8 };
 enum { DYNF_DEEPER = 1,    // calls were left at the first level the sequence did not launch
        DYNF_POOL_FULL = 2 }; // more leaves than the sequence's pool holds
+// the job's counters: 32-bit slots at the head of the zero arena (EnumBuffers::counters), all zero when a job starts
+enum { SEARCH_LEVELS = Caps::K + 2,       // level launches after which no search has a call left
+       CNT_LEVELS = 0,                    // [SEARCH_LEVELS + 1] calls made at each depth (EnumArgs::level_count)
+       CNT_LEAVES = Caps::K + 3,          // leaves found
+       CNT_NODES = (Caps::K + 5) & ~1,    // calls made: 64 bit, so at the first even slot past the leaves (two slots)
+       CNT_UNHANDLED = Caps::K + 7,       // reads F5 turned down
+       CNT_DYN = Caps::K + 8,             // [DYN_COUNT] the scans' results
+       CNT_QUEUE = CNT_DYN + DYN_COUNT,   // [2] F5's read queue (FusedScoreArgs::queue)
+       N_COUNTERS = CNT_QUEUE + 2 };
+static_assert(CNT_LEVELS + SEARCH_LEVELS + 1 == CNT_LEAVES && CNT_NODES > CNT_LEAVES && CNT_NODES + 2 <= CNT_UNHANDLED, "the counters' slots overlap");
 
 __device__ inline int block_exclusive_scan(const int v, int* wave_sums /* LDS [blockDim.x / 64 + 1] */, int* total)
 {
@@ -2169,40 +2179,26 @@ __global__ __launch_bounds__(64 * WAVES) void stage3_kernel(const Stage3Args a)
 // ---------------------------------------------------------------------------------------------------------------------
 // buffers: grown on demand, kept for the life of the process (one job after the other reuses them)
 
-struct DevBuf
+template <bool PINNED>
+struct Buf
 {
     void* p = nullptr;
     size_t cap = 0;
     int reserve(const size_t bytes)
     {
         if (bytes <= cap) return 0;
-        if (p) (void)skrt::free_(p);
+        if (p) (void)(PINNED ? skrt::hostFree(p) : skrt::free_(p));
         p = nullptr;
         cap = 0;
         const size_t want = bytes + bytes / 4 + 4096;
-        SK_HIP(skrt::malloc_(&p, want));
+        SK_HIP(PINNED ? skrt::hostMalloc(&p, want) : skrt::malloc_(&p, want));
         cap = want;
         return 0;
     }
     template <typename T> T* as() const { return static_cast<T*>(p); }
 };
-struct HostBuf // pinned
-{
-    void* p = nullptr;
-    size_t cap = 0;
-    int reserve(const size_t bytes)
-    {
-        if (bytes <= cap) return 0;
-        if (p) (void)skrt::hostFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = bytes + bytes / 4 + 4096;
-        SK_HIP(skrt::hostMalloc(&p, want));
-        cap = want;
-        return 0;
-    }
-    template <typename T> T* as() const { return static_cast<T*>(p); }
-};
+using DevBuf = Buf<false>;
+using HostBuf = Buf<true>; // pinned
 
 struct View // a piece of one of the arenas below
 {
@@ -2234,6 +2230,32 @@ EnumBuffers& bufs()
 {
     static EnumBuffers b;
     return b;
+}
+
+// a job's reservations, as tables: a device buffer holds at least 256 bytes (an empty array still has an address), a pinned one 64 bytes
+// more than asked for (job_stage_out_kernel writes whole 16-byte words)
+int reserve_dev(std::initializer_list<std::pair<DevBuf&, size_t>> wants) // { buffer, bytes }, ...
+{
+    for (const auto& w : wants)
+        if (w.first.reserve(std::max<size_t>(w.second, 256))) return 1;
+    return 0;
+}
+int reserve_pinned(std::initializer_list<std::pair<HostBuf&, size_t>> wants)
+{
+    for (const auto& w : wants)
+        if (w.first.reserve(w.second + 64)) return 1;
+    return 0;
+}
+// copies on the job's stream; nothing is submitted for zero bytes
+int copy_up(hipStream_t st, const DevBuf& dst, const void* src, const size_t bytes)
+{
+    if (bytes > 0) SK_HIP(skrt::memcpyAsync(dst.p, src, bytes, hipMemcpyHostToDevice, st));
+    return 0;
+}
+int copy_down(hipStream_t st, const HostBuf& dst, const DevBuf& src, const size_t bytes)
+{
+    if (bytes > 0) SK_HIP(skrt::memcpyAsync(dst.p, src.p, bytes, hipMemcpyDeviceToHost, st));
+    return 0;
 }
 
 } // namespace
@@ -2316,90 +2338,101 @@ extern "C" void sk_enum_device_job_counts(int64_t* one_wait, int64_t* one_wait_r
     if (staged) *staged = g_jobs_staged;
 }
 
-// one_wait: the job as ONE fixed sequence of submissions and one host wait (see job_scan_kernel); *redo is set when the sequence's
-// assumptions did not hold for this job and nothing of `out` is valid: the caller runs it again with one_wait = false
-static int enum_device_run_impl(const SkEnumInput* in, SkEnumOutput* out, const bool one_wait, bool* redo)
+// ---------------------------------------------------------------------------------------------------------------------
+// the job driver.  A job is prepared once (start_job, plan_job: capacities, the arenas' layout, reservations, the packed input on its way up)
+// and then run either as ONE fixed sequence of submissions with one host wait (run_one_wait) or the staged way, with a wait after the
+// search, one after the sets and one at the end (run_staged).  One builder per kernel argument struct: its parameters are what differs
+// between the two runs.
+namespace
 {
-    SK_REQUIRE_INIT();
-    skrt::wakeHint();
-    if (!in || !out) return sk_fail("sk_enum_device_run: null argument");
-    std::memset(out, 0, sizeof(*out));
-    out->generation = ++g_generation;
-    g_n_cals = 0;
-    g_scores = nullptr;
-    g_cals_gathered = false;
-    g_last.valid = false;
-    const int n = in->n_reads;
-    if (n < 0 || in->n_tab < 0) return sk_fail("sk_enum_device_run: negative count");
-    SkContext& ctx = sk_ctx();
-    SK_HIP(skrt::setDevice(ctx.device));
-    hipStream_t st = ctx.stream;
+struct JobPlan
+{
+    const SkEnumInput* in = nullptr;
     EnumBuffers& B = bufs();
-    const bool timing = std::getenv("SK_ENUM_TIMING") != nullptr;
-    const auto t_begin = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
+    hipStream_t st = nullptr;
+    bool one_wait = false, with_stage3 = false;
+    int n = 0;
+    int64_t n_bases = 0, frame_cap = 0, pool_cap = 0; // capacities: calls in flight at one depth, leaves found (before duplicates are dropped)
+    int W = 0;                                        // words of a read's event mask
+    int max_order = 0;                                // the deepest indel order a read of the job arrives with
+    size_t in_bytes = 0, zero_bytes = 0, minmax_bytes = 0, mask_bytes = 0; // the arenas
+    size_t minmax_split = 0;                                               // win_begin, ins_lo before it; win_end, ins_hi from it on
+    PJob dj;
+    // stage 3: a read with at most light_cals candidate alignments is the first launch's; a block keeps up to lds_cals of them in LDS
+    int light_cals = S3_LIGHT_CALS, lds_cals = S3_LDS_CALS;
+    bool timing = false; // $SK_ENUM_TIMING
+    std::chrono::steady_clock::time_point t_begin;
+
+    void lap(const char* what) const
+    {
         if (!timing) return;
         (void)skrt::streamSynchronize(st);
         std::fprintf(stderr, "[enum-dev] %-28s t=%.3f ms\n", what,
                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
-    };
+    }
+};
 
-    const int64_t n_bases = n ? in->read_off[n] : 0;
+struct Piece // of an arena, at a 256-byte offset
+{
+    View* view;
+    const void* src; // in_arena: where the bytes come from
+    size_t bytes, off;
+};
+size_t lay_out(Piece* pc, const int n_pieces)
+{
+    size_t at = 0;
+    for (int i = 0; i < n_pieces; ++i) {
+        pc[i].off = at;
+        at += (pc[i].bytes + 255) & ~size_t(255);
+    }
+    return at;
+}
+
+// everything about a job that is known before its first submission.  one_wait: the buffers between the search and stage 3 will be sized
+// by the pool's capacity, and cal_off is made on the device (a piece of the zero arena)
+int plan_job(const SkEnumInput* in, const bool one_wait, JobPlan& p)
+{
+    EnumBuffers& B = p.B;
+    p.in = in;
+    p.st = sk_ctx().stream;
+    p.one_wait = one_wait;
+    const int n = p.n = in->n_reads;
+    const int64_t n_bases = p.n_bases = n ? in->read_off[n] : 0;
     // capacities: calls in flight at one depth and leaves found (before duplicates are dropped), for the whole job; a job that
     // needs more has the reads that did not fit enumerated on the host
     // (sized by the job; the ceilings -- two level buffers of 2^23 frames, 2^25 leaves: ~21 GB in all -- are a fraction of 288 GB of HBM
     // and let a job of 2^16 reads with ~90 candidate alignments each run whole)
-    int64_t frame_cap = std::min<int64_t>(std::max<int64_t>(int64_t(n) * 128, 1 << 18), 1 << 23);
-    int64_t pool_cap = std::min<int64_t>(std::max<int64_t>(int64_t(n) * 512, 1 << 19), int64_t(32) << 20);
-    if (const char* e = std::getenv("SK_ENUM_TEST_CAPS")) { // tests: small capacities, so that the overflow paths run
+    p.frame_cap = std::min<int64_t>(std::max<int64_t>(int64_t(n) * 128, 1 << 18), 1 << 23);
+    p.pool_cap = std::min<int64_t>(std::max<int64_t>(int64_t(n) * 512, 1 << 19), int64_t(32) << 20);
+    const char* const test_caps = std::getenv("SK_ENUM_TEST_CAPS"); // tests: small capacities, so that the overflow paths run
+    if (test_caps) {
         long long fc = 0, pc = 0;
-        if (std::sscanf(e, "%lld,%lld", &fc, &pc) == 2 && fc > 0 && pc > 0) {
-            frame_cap = std::max<int64_t>(fc, n);
-            pool_cap = pc;
+        if (std::sscanf(test_caps, "%lld,%lld", &fc, &pc) == 2 && fc > 0 && pc > 0) {
+            p.frame_cap = std::max<int64_t>(fc, n);
+            p.pool_cap = pc;
         }
     }
-    bool test_caps = false;
-    if (const char* e = std::getenv("SK_ENUM_TEST_CAPS")) test_caps = (e[0] != 0);
     // one sequence: the buffers between the search and stage 3 are sized by the pool's capacity instead of by counts the host would have
     // to wait for -- 256 leaves per read (at least 2^17) cover every WGS-like job; one that needs more is run again the staged way
-    if (one_wait && !test_caps) pool_cap = std::min<int64_t>(pool_cap, std::max<int64_t>(int64_t(n) * 256, 1 << 17));
-    const int n_counters = Caps::K + 8 + DYN_COUNT + 2; // (+ 2: F5's read queue, FusedScoreArgs::queue)  // level counts [0, K+3), leaves, calls made (64 bit), F5's unhandled reads; the scans' results
-#define RES(buf, bytes) \
-    if (B.buf.reserve(std::max<size_t>(size_t(bytes), 256))) return 1
-#define HRES(buf, bytes) \
-    if (B.buf.reserve(size_t(bytes) + 64)) return 1
-    RES(level_a, sizeof(PFrame) * size_t(frame_cap));
-    RES(level_b, sizeof(PFrame) * size_t(frame_cap));
-    RES(pool, sizeof(PCal) * size_t(pool_cap));
-    RES(leaf_read, 4 * size_t(pool_cap));
-    RES(leaf_hash, 4 * size_t(pool_cap));
-    RES(raw_off, 4 * size_t(n + 1));
-    RES(win_len, 4 * size_t(n));
-    RES(n_ins, 4 * size_t(n));
-    RES(ins_idx, 2 * size_t(n) * INS_CAP);
-    RES(ins_off, 4 * size_t(n) * INS_CAP);
-    RES(cal_off, 4 * size_t(n + 1));
-    RES(hap_off, 8 * size_t(n + 1));
-    HRES(h_raw_off, 4 * size_t(n + 1));
-    HRES(h_cal_off, 4 * size_t(n + 1));
-    HRES(h_hap_off, 8 * size_t(n + 1));
-    const bool with_stage3 = in->want_scores && in->want_stage3;
-    const int W = sk_ent_evmask_words(std::max(in->max_read_len, 0));
-    // ---- the arenas: pieces at 256-byte offsets
-    struct Piece
-    {
-        View* view;
-        const void* src; // in_arena: where the bytes come from
-        size_t bytes, off;
-    };
-    auto lay_out = [](Piece* pc, const int n_pieces) {
-        size_t at = 0;
-        for (int i = 0; i < n_pieces; ++i) {
-            pc[i].off = at;
-            at += (pc[i].bytes + 255) & ~size_t(255);
+    if (one_wait && !(test_caps && test_caps[0])) p.pool_cap = std::min<int64_t>(p.pool_cap, std::max<int64_t>(int64_t(n) * 256, 1 << 17));
+    const bool s3 = p.with_stage3 = in->want_scores && in->want_stage3;
+    const int W = p.W = sk_ent_evmask_words(std::max(in->max_read_len, 0));
+    for (int r = 0; r < n; ++r) p.max_order = std::max(p.max_order, int(in->reads[r].n_order));
+    if (const char* e = std::getenv("SK_STAGE3_TEST_LDS_CALS")) { // tests: small capacities, so that the second launch and the HBM arrays run
+        int a = 0, b = 0;
+        if (std::sscanf(e, "%d,%d", &a, &b) == 2 && a > 0 && b >= a && b <= S3_LDS_CALS) {
+            p.light_cals = a;
+            p.lds_cals = b;
         }
-        return at;
-    };
+    }
+    if (reserve_dev({ { B.level_a, sizeof(PFrame) * size_t(p.frame_cap) }, { B.level_b, sizeof(PFrame) * size_t(p.frame_cap) },
+                      { B.pool, sizeof(PCal) * size_t(p.pool_cap) }, { B.leaf_read, 4 * size_t(p.pool_cap) }, { B.leaf_hash, 4 * size_t(p.pool_cap) },
+                      { B.raw_off, 4 * size_t(n + 1) }, { B.win_len, 4 * size_t(n) }, { B.n_ins, 4 * size_t(n) },
+                      { B.ins_idx, 2 * size_t(n) * INS_CAP }, { B.ins_off, 4 * size_t(n) * INS_CAP },
+                      { B.cal_off, 4 * size_t(n + 1) }, { B.hap_off, 8 * size_t(n + 1) } }) ||
+        reserve_pinned({ { B.h_raw_off, 4 * size_t(n + 1) }, { B.h_cal_off, 4 * size_t(n + 1) }, { B.h_hap_off, 8 * size_t(n + 1) } }))
+        return 1;
+    // ---- the arenas: pieces at 256-byte offsets
     Piece ins_p[] = {
         { &B.tab, in->tab, sizeof(PIndel) * size_t(in->n_tab), 0 },
         { &B.ins, in->ins_pool, size_t(in->ins_pool_len), 0 },
@@ -2409,37 +2442,34 @@ static int enum_device_run_impl(const SkEnumInput* in, SkEnumOutput* out, const 
         { &B.read_off, in->read_off, sizeof(int64_t) * size_t(n + 1), 0 },
         { &B.read_code, in->read_code, size_t(n_bases), 0 },
         { &B.read_qual, in->read_qual, size_t(n_bases), 0 },
-        { &B.r2i, in->r2i, with_stage3 ? 8 * size_t(in->n_tab) : 0, 0 },
-        { &B.i2r, in->i2r, with_stage3 ? 8 * size_t(in->n_tab) : 0, 0 },
-        { &B.orig, in->orig, with_stage3 ? 4 * size_t(in->n_tab) : 0, 0 },
-        { &B.map_level, in->map_level, with_stage3 ? 4 * size_t(n) : 0, 0 },
+        { &B.r2i, in->r2i, s3 ? 8 * size_t(in->n_tab) : 0, 0 },
+        { &B.i2r, in->i2r, s3 ? 8 * size_t(in->n_tab) : 0, 0 },
+        { &B.orig, in->orig, s3 ? 4 * size_t(in->n_tab) : 0, 0 },
+        { &B.map_level, in->map_level, s3 ? 4 * size_t(n) : 0, 0 },
         // (no source: the code images are written into the mirror below)
         { &B.ref_code, nullptr, size_t(std::max(in->ref_len, 0)) + 2 * size_t(F5_CODE_PAD), 0 },
         { &B.ins_code, nullptr, size_t(in->ins_pool_len), 0 },
     };
     const int n_ins_p = int(sizeof(ins_p) / sizeof(ins_p[0]));
-    const size_t in_bytes = lay_out(ins_p, n_ins_p);
+    p.in_bytes = lay_out(ins_p, n_ins_p);
     // (the order matters: what the host reads after the search is one run, what it reads after the layout another)
     Piece zero_p[] = {
-        { &B.counters, nullptr, 4 * size_t(n_counters), 0 }, { &B.warn, nullptr, 4 * size_t(n), 0 },    { &B.n_raw, nullptr, 4 * size_t(n), 0 },
+        { &B.counters, nullptr, 4 * size_t(N_COUNTERS), 0 }, { &B.warn, nullptr, 4 * size_t(n), 0 },    { &B.n_raw, nullptr, 4 * size_t(n), 0 },
         { &B.status, nullptr, 4 * size_t(n), 0 },            { &B.hap_len, nullptr, 4 * size_t(n), 0 }, { &B.fill, nullptr, 4 * size_t(n), 0 },
         { &B.n_uniq, nullptr, 4 * size_t(n), 0 },            { &B.consulted, nullptr, size_t(in->n_tab) + 1, 0 },
         { &B.cal_off_z, nullptr, one_wait ? 4 * size_t(n + 1) : 0, 0 }, // (one sequence: cal_off is made on the device and comes back with the arena)
     };
     View* zero_host[] = { &B.h_counters, &B.h_warn, &B.h_n_raw, &B.h_status, &B.h_hap_len, nullptr, &B.h_n_uniq, &B.h_consulted, &B.h_cal_off_z };
     const int n_zero_p = int(sizeof(zero_p) / sizeof(zero_p[0]));
-    const size_t zero_bytes = lay_out(zero_p, n_zero_p);
+    p.zero_bytes = lay_out(zero_p, n_zero_p);
     Piece minmax_p[] = { { &B.win_begin, nullptr, 4 * size_t(n), 0 }, { &B.ins_lo, nullptr, 4 * size_t(n), 0 },
                          { &B.win_end, nullptr, 4 * size_t(n), 0 },   { &B.ins_hi, nullptr, 4 * size_t(n), 0 } };
-    const size_t minmax_bytes = lay_out(minmax_p, 4);
+    p.minmax_bytes = lay_out(minmax_p, 4);
+    p.minmax_split = minmax_p[2].off;
     Piece mask_p[] = { { &B.evmask, nullptr, 4 * (size_t(n) * size_t(W) + 1), 0 }, { &B.addmask, nullptr, 4 * (size_t(n) * size_t(W) + 1), 0 } };
-    const size_t mask_bytes = lay_out(mask_p, 2);
-    RES(in_arena, in_bytes);
-    RES(zero_arena, zero_bytes);
-    RES(minmax_arena, minmax_bytes);
-    RES(mask_arena, mask_bytes);
-    HRES(h_in_arena, in_bytes);
-    HRES(h_zero_arena, zero_bytes);
+    p.mask_bytes = lay_out(mask_p, 2);
+    if (reserve_dev({ { B.in_arena, p.in_bytes }, { B.zero_arena, p.zero_bytes }, { B.minmax_arena, p.minmax_bytes }, { B.mask_arena, p.mask_bytes } })) return 1;
+    if (reserve_pinned({ { B.h_in_arena, p.in_bytes }, { B.h_zero_arena, p.zero_bytes } })) return 1;
     for (int i = 0; i < n_ins_p; ++i) {
         ins_p[i].view->p = static_cast<char*>(B.in_arena.p) + ins_p[i].off;
         if (ins_p[i].bytes && ins_p[i].src) std::memcpy(static_cast<char*>(B.h_in_arena.p) + ins_p[i].off, ins_p[i].src, ins_p[i].bytes);
@@ -2460,395 +2490,139 @@ static int enum_device_run_impl(const SkEnumInput* in, SkEnumOutput* out, const 
     }
     for (int i = 0; i < 4; ++i) minmax_p[i].view->p = static_cast<char*>(B.minmax_arena.p) + minmax_p[i].off;
     for (int i = 0; i < 2; ++i) mask_p[i].view->p = static_cast<char*>(B.mask_arena.p) + mask_p[i].off;
-    // a run of the zero arena, device -> its pinned mirror
-    auto fetch_zero = [&](const View& first, const View& last, const size_t last_bytes) -> int {
-        const size_t a0 = size_t(static_cast<char*>(first.p) - static_cast<char*>(B.zero_arena.p));
-        const size_t a1 = size_t(static_cast<char*>(last.p) - static_cast<char*>(B.zero_arena.p)) + last_bytes;
-        SK_HIP(skrt::memcpyAsync(static_cast<char*>(B.h_zero_arena.p) + a0, static_cast<char*>(B.zero_arena.p) + a0, a1 - a0, hipMemcpyDeviceToHost, st));
-        return 0;
-    };
 
-#define H2D(buf, src, bytes) \
-    if ((bytes) > 0) SK_HIP(skrt::memcpyAsync(B.buf.p, src, size_t(bytes), hipMemcpyHostToDevice, st))
-#define D2H(hbuf, buf, bytes) \
-    if ((bytes) > 0) SK_HIP(skrt::memcpyAsync(B.hbuf.p, B.buf.p, size_t(bytes), hipMemcpyDeviceToHost, st))
-    static const bool stage_by_kernel = !(std::getenv("SK_ENUM_STAGE_COPIES") != nullptr); // ($SK_ENUM_STAGE_COPIES: the copy / fill calls, for A-B runs)
-    if (one_wait && stage_by_kernel) {
-        const uint32_t n_in16 = uint32_t(in_bytes / 16), n_zero16 = uint32_t(zero_bytes / 16); // (pieces sit at 256-byte offsets)
-        const int blocks = int(std::min<size_t>(std::max<size_t>((std::max(in_bytes, zero_bytes) / 16 + 255) / 256, 1), 256));
-        SK_LAUNCH(job_stage_in_kernel, dim3(blocks), dim3(256), 0, st, static_cast<const uint4*>(B.h_in_arena.p), static_cast<uint4*>(B.in_arena.p), n_in16,
-                           static_cast<uint4*>(B.zero_arena.p), n_zero16);
+    p.dj.tab = B.tab.as<PIndel>();
+    p.dj.n_tab = in->n_tab;
+    p.dj.max_toggle = B.toggle.as<uint32_t>();
+    p.dj.n_max_toggle = in->n_max_toggle;
+    p.dj.sample_count = in->sample_count;
+    p.dj.max_read_indel_toggle = in->max_read_indel_toggle;
+    p.dj.max_candidate_indel_density = in->max_candidate_indel_density;
+    p.dj.is_haplotyping_enabled = in->is_haplotyping_enabled;
+    p.dj.max_indel_size = in->max_indel_size;
+    p.dj.consulted = B.consulted.as<uint8_t>();
+    p.dj.max_nodes = 0;
+    return 0;
+}
+
+// the copy / fill calls instead of the job_stage_*_kernel launches of a one-sequence run ($SK_ENUM_STAGE_COPIES, for A-B runs)
+bool stage_by_kernel()
+{
+    static const bool by_kernel = std::getenv("SK_ENUM_STAGE_COPIES") == nullptr;
+    return by_kernel;
+}
+
+// the job's way in: the packed input up, the zero arena zeroed
+int stage_in(const JobPlan& p)
+{
+    EnumBuffers& B = p.B;
+    if (p.one_wait && stage_by_kernel()) {
+        const uint32_t n_in16 = uint32_t(p.in_bytes / 16), n_zero16 = uint32_t(p.zero_bytes / 16); // (pieces sit at 256-byte offsets)
+        const int blocks = int(std::min<size_t>(std::max<size_t>((std::max(p.in_bytes, p.zero_bytes) / 16 + 255) / 256, 1), 256));
+        SK_LAUNCH(job_stage_in_kernel, dim3(blocks), dim3(256), 0, p.st, static_cast<const uint4*>(B.h_in_arena.p), static_cast<uint4*>(B.in_arena.p), n_in16,
+                  static_cast<uint4*>(B.zero_arena.p), n_zero16);
     } else {
-        if (in_bytes > 0) SK_HIP(skrt::memcpyAsync(B.in_arena.p, B.h_in_arena.p, in_bytes, hipMemcpyHostToDevice, st));
-        SK_HIP(skrt::memsetAsync(B.zero_arena.p, 0, zero_bytes, st));
+        if (copy_up(p.st, B.in_arena, B.h_in_arena.p, p.in_bytes)) return 1;
+        SK_HIP(skrt::memsetAsync(B.zero_arena.p, 0, p.zero_bytes, p.st));
     }
+    return 0;
+}
 
-    int32_t* h_cal_off = B.h_cal_off.as<int32_t>();
-    h_cal_off[0] = 0;
+// a run of the zero arena, device -> its pinned mirror
+int fetch_zero(const JobPlan& p, const View& first, const View& last, const size_t last_bytes)
+{
+    char* const dev = static_cast<char*>(p.B.zero_arena.p);
+    const size_t a0 = size_t(static_cast<char*>(first.p) - dev);
+    const size_t a1 = size_t(static_cast<char*>(last.p) - dev) + last_bytes;
+    SK_HIP(skrt::memcpyAsync(static_cast<char*>(p.B.h_zero_arena.p) + a0, dev + a0, a1 - a0, hipMemcpyDeviceToHost, p.st));
+    return 0;
+}
+
+// a new generation of results, the plan, the input on its way; a job without reads is complete after this
+int start_job(const SkEnumInput* in, SkEnumOutput* out, const bool one_wait, JobPlan& p)
+{
+    SK_REQUIRE_INIT();
+    skrt::wakeHint();
+    if (!in || !out) return sk_fail("sk_enum_device_run: null argument");
+    std::memset(out, 0, sizeof(*out));
+    out->generation = ++g_generation;
+    g_n_cals = 0;
+    g_scores = nullptr;
+    g_cals_gathered = false;
+    g_last.valid = false;
+    if (in->n_reads < 0 || in->n_tab < 0) return sk_fail("sk_enum_device_run: negative count");
+    SK_HIP(skrt::setDevice(sk_ctx().device));
+    p.timing = std::getenv("SK_ENUM_TIMING") != nullptr;
+    p.t_begin = std::chrono::steady_clock::now();
+    if (plan_job(in, one_wait, p) || stage_in(p)) return 1;
+    EnumBuffers& B = p.B;
+    B.h_cal_off.as<int32_t>()[0] = 0;
     out->status = B.h_status.as<int32_t>();
-    out->cal_off = h_cal_off;
+    out->cal_off = B.h_cal_off.as<int32_t>();
     out->consulted = B.h_consulted.as<uint8_t>();
-    if (n == 0) {
+    if (p.n == 0) {
         std::memset(B.h_consulted.p, 0, size_t(in->n_tab));
         return 0;
     }
-    if (n > frame_cap) return sk_fail("sk_enum_device_run: more reads in one job than the device pipeline holds");
+    if (p.n > p.frame_cap) return sk_fail("sk_enum_device_run: more reads in one job than the device pipeline holds");
+    p.lap("H2D");
+    return 0;
+}
 
-    PJob dj;
-    dj.tab = B.tab.as<PIndel>();
-    dj.n_tab = in->n_tab;
-    dj.max_toggle = B.toggle.as<uint32_t>();
-    dj.n_max_toggle = in->n_max_toggle;
-    dj.sample_count = in->sample_count;
-    dj.max_read_indel_toggle = in->max_read_indel_toggle;
-    dj.max_candidate_indel_density = in->max_candidate_indel_density;
-    dj.is_haplotyping_enabled = in->is_haplotyping_enabled;
-    dj.max_indel_size = in->max_indel_size;
-    dj.consulted = B.consulted.as<uint8_t>();
-    dj.max_nodes = 0;
+// ---- the kernels' arguments
 
-    // ---- E1: the search, one launch per depth
-    EnumArgs ea;
-    ea.job = dj;
+// root_sets_minmax: the root launch initialises the four minmax arrays (else they are filled before pool_bounds_kernel)
+EnumArgs enum_args(const JobPlan& p, const bool root_sets_minmax)
+{
+    EnumBuffers& B = p.B;
+    int32_t* const counters = B.counters.as<int32_t>();
+    EnumArgs ea{}; // (level_in, level_out, depth: launch_search)
+    ea.job = p.dj;
     ea.reads = B.reads.as<PRead>();
-    ea.n_reads = n;
-    ea.frame_cap = int32_t(frame_cap);
-    ea.level_count = B.counters.as<int32_t>();
+    ea.n_reads = p.n;
+    ea.frame_cap = int32_t(p.frame_cap);
+    ea.level_count = counters + CNT_LEVELS;
     ea.pool = B.pool.as<PCal>();
     ea.leaf_read = B.leaf_read.as<int32_t>();
     ea.leaf_hash = B.leaf_hash.as<uint32_t>();
-    ea.pool_cap = int32_t(pool_cap);
-    ea.n_leaves = B.counters.as<int32_t>() + (Caps::K + 3);
-    ea.n_nodes = reinterpret_cast<unsigned long long*>(B.counters.as<int32_t>() + (Caps::K + 4) + ((Caps::K + 4) & 1));
+    ea.pool_cap = int32_t(p.pool_cap);
+    ea.n_leaves = counters + CNT_LEAVES;
+    ea.n_nodes = reinterpret_cast<unsigned long long*>(counters + CNT_NODES);
     ea.n_raw = B.n_raw.as<int32_t>();
     ea.status = B.status.as<int32_t>();
     ea.warn = B.warn.as<int32_t>();
-    ea.min_cells_a = ea.min_cells_b = ea.max_cells_a = ea.max_cells_b = nullptr;
-    lap("H2D");
-    const auto t_setup = std::chrono::steady_clock::now();
-    if (one_wait) {
-        // ---- the job as one fixed sequence: ~20 submissions, no host decision between them, ONE wait.  Everything the host used to
-        // compute between waits is computed by job_scan_kernel; every buffer is sized by a capacity known now; launches whose size the
-        // host does not know cover the capacity with a grid-stride loop (or a block per read of the job that leaves at once).
-        const int32_t n_cap = int32_t(pool_cap); // leaves, grouped leaves and candidate alignments are all at most this many
-        RES(grouped, 4 * size_t(n_cap));
-        RES(ghash, 4 * size_t(n_cap));
-        RES(gkey, 16 * size_t(n_cap));
-        RES(dup, size_t(n_cap));
-        RES(sorted, 4 * size_t(n_cap));
-        RES(n_seg8, size_t(n_cap));
-        RES(scores, 8 * size_t(n_cap));
-        RES(s3_order, 4 * size_t(n_cap));
-        RES(s3_smooth, 8 * size_t(n_cap));
-        RES(s3_flag, size_t(n_cap));
-        RES(s3_rm_type, size_t(n_bases));
-        RES(s3_rm_pos, 4 * size_t(n_bases));
-        RES(s3_key, 16 * size_t(n_cap));
-        RES(s3_sorted_score, 8 * size_t(n_cap));
-        RES(s3_sorted_hash, 4 * size_t(n_cap));
-        RES(s3_next_same, 4 * size_t(n_cap));
-        RES(s3_removed, size_t(n_cap));
-        RES(s3_range_end, 4 * size_t(n_cap));
-        RES(s3_out, sizeof(sk3::Out) * size_t(n));
-        RES(s3_list, 4 * size_t(n));
-        HRES(h_s3_out, sizeof(sk3::Out) * size_t(n));
-        int32_t* const dyn = B.counters.as<int32_t>() + (Caps::K + 8);
-        const int32_t* const h_dyn = B.h_counters.as<int32_t>() + (Caps::K + 8);
-        int32_t* const n_unhandled = B.counters.as<int32_t>() + (Caps::K + 7);
+    ea.min_cells_a = root_sets_minmax ? B.win_begin.as<int32_t>() : nullptr;
+    ea.min_cells_b = root_sets_minmax ? B.ins_lo.as<int32_t>() : nullptr;
+    ea.max_cells_a = root_sets_minmax ? B.win_end.as<int32_t>() : nullptr;
+    ea.max_cells_b = root_sets_minmax ? B.ins_hi.as<int32_t>() : nullptr;
+    return ea;
+}
 
-        // E1: root + the levels up to the deepest order of the job (+ 2: indels that join an order on the way); whether calls were left
-        // for a deeper level is looked at on the device (scan 1) and reported with the results
-        PFrame* buf[2] = { B.level_a.as<PFrame>(), B.level_b.as<PFrame>() };
-        ea.min_cells_a = B.win_begin.as<int32_t>();
-        ea.min_cells_b = B.ins_lo.as<int32_t>();
-        ea.max_cells_a = B.win_end.as<int32_t>();
-        ea.max_cells_b = B.ins_hi.as<int32_t>();
-        ea.level_in = nullptr;
-        ea.level_out = buf[0];
-        ea.depth = -1;
-        SK_LAUNCH(root_kernel, dim3((n + 63) / 64), dim3(64), 0, st, ea);
-        int max_order = 0;
-        for (int r = 0; r < n; ++r) max_order = std::max(max_order, int(in->reads[r].n_order));
-        int n_levels = std::min(max_order + 3, int(Caps::K) + 2);
-        if (const char* e = std::getenv("SK_ENUM_TEST_LEVELS")) // tests: too few levels, so that the device reports it and the job runs again
-            if (std::atoi(e) > 0) n_levels = std::min(n_levels, std::atoi(e));
-        {
-            const size_t lds = 64 * sizeof(PFrame);
-            // (a level of this job has at most a few frames per read: blocks beyond that would only read the count and leave)
-            const int blocks = int(std::min<int64_t>(std::min<int64_t>((frame_cap + 63) / 64, 1024), std::max<int64_t>(n, 16)));
-            for (int d = 0; d < n_levels; ++d) {
-                ea.level_in = buf[d & 1];
-                ea.level_out = buf[(d + 1) & 1];
-                ea.depth = d;
-                SK_LAUNCH(level_kernel, dim3(blocks), dim3(64), lds, st, ea);
-            }
-        }
-        // scan 1: raw_off
-        ScanArgs sc;
-        std::memset(&sc, 0, sizeof(sc));
-        sc.n_reads = n;
-        sc.status = ea.status;
-        sc.count = ea.n_raw;
-        sc.off = B.raw_off.as<int32_t>();
-        sc.dyn = dyn;
-        sc.level_count = ea.level_count;
-        sc.first_level_not_launched = (n_levels >= int(Caps::K) + 2) ? -1 : n_levels;
-        sc.n_leaves = ea.n_leaves;
-        sc.pool_cap = n_cap;
-        SK_LAUNCH(job_scan_kernel<false>, dim3(1), dim3(1024), 0, st, sc);
-        // E2
-        SetArgs sa;
-        std::memset(&sa, 0, sizeof(sa));
-        sa.pool = ea.pool;
-        sa.leaf_read = ea.leaf_read;
-        sa.leaf_hash = ea.leaf_hash;
-        sa.status = ea.status;
-        sa.n_reads = n;
-        sa.n_leaves = n_cap;
-        sa.n_leaves_dev = ea.n_leaves;
-        sa.raw_off = B.raw_off.as<int32_t>();
-        sa.fill = B.fill.as<int32_t>();
-        sa.grouped = B.grouped.as<int32_t>();
-        sa.ghash = B.ghash.as<uint32_t>();
-        sa.gkey = B.gkey.as<ulonglong2>();
-        sa.dup = B.dup.as<uint8_t>();
-        sa.n_uniq = B.n_uniq.as<int32_t>();
-        sa.cal_off = B.cal_off_z.as<int32_t>();
-        sa.sorted = B.sorted.as<int32_t>();
-        // (grids for counts the host has not seen: enough blocks for ~64 leaves per read, the loops cover the rest)
-        const int e2_blocks = int(std::min<int64_t>(std::max<int64_t>((int64_t(n) * 64 + 255) / 256, 8), 2048));
-        SK_LAUNCH(group_kernel, dim3(e2_blocks), dim3(256), 0, st, sa);
-        SK_LAUNCH(dedupe_kernel, dim3(e2_blocks), dim3(256), 0, st, sa);
-        // scan 2: cal_off, stage 3's lists
-        int light_cals = S3_LIGHT_CALS, lds_cals = S3_LDS_CALS;
-        if (const char* e = std::getenv("SK_STAGE3_TEST_LDS_CALS")) {
-            int a = 0, b = 0;
-            if (std::sscanf(e, "%d,%d", &a, &b) == 2 && a > 0 && b >= a && b <= S3_LDS_CALS) {
-                light_cals = a;
-                lds_cals = b;
-            }
-        }
-        sc.count = B.n_uniq.as<int32_t>();
-        sc.off = B.cal_off_z.as<int32_t>();
-        sc.list = B.s3_list.as<int32_t>();
-        sc.light_cals = light_cals;
-        SK_LAUNCH(job_scan_kernel<true>, dim3(1), dim3(1024), 0, st, sc);
-        SK_LAUNCH(rank_kernel, dim3(e2_blocks), dim3(256), 0, st, sa);
-        // L1
-        FlatArgs fa;
-        std::memset(&fa, 0, sizeof(fa));
-        fa.job = dj;
-        fa.ins_pool = B.ins.as<char>();
-        fa.ref = B.ref.as<char>();
-        fa.ref_code = B.ref_code.as<uint8_t>() + F5_CODE_PAD;
-        fa.ins_code = B.ins_code.as<uint8_t>();
-        fa.ref_offset = in->ref_offset;
-        fa.ref_len = in->ref_len;
-        fa.n_reads = n;
-        fa.n_cals = n_cap;
-        fa.n_cals_on_device = 1;
-        fa.pool = ea.pool;
-        fa.list = B.sorted.as<int32_t>();
-        fa.status = ea.status;
-        fa.read_off = B.read_off.as<int64_t>();
-        fa.read_code = B.read_code.as<uint8_t>();
-        fa.cal_off = B.cal_off_z.as<int32_t>();
-        fa.win_begin = B.win_begin.as<int32_t>();
-        fa.win_len = B.win_len.as<int32_t>();
-        fa.hap_len = B.hap_len.as<int32_t>();
-        fa.n_ins = B.n_ins.as<int32_t>();
-        fa.ins_idx = B.ins_idx.as<int16_t>();
-        fa.ins_off = B.ins_off.as<int32_t>();
-        fa.win_end = B.win_end.as<int32_t>();
-        fa.ins_lo = B.ins_lo.as<int32_t>();
-        fa.ins_hi = B.ins_hi.as<int32_t>();
-        fa.n_seg8 = B.n_seg8.as<uint8_t>();
-        fa.max_read_len = in->max_read_len;
-        fa.ref_outside = dyn + DYN_REF_OUTSIDE;
-        SK_LAUNCH(pool_bounds_kernel, dim3(e2_blocks), dim3(256), 0, st, fa);
-        SK_LAUNCH(pool_layout_kernel, dim3((n + 63) / 64), dim3(64), 0, st, fa);
-        // F5
-        FusedScoreArgs fs;
-        fs.f = fa;
-        fs.read_qual = B.read_qual.as<uint8_t>();
-        fs.tab = ctx.dev_tables;
-        fs.scores = B.scores.as<double>();
-        fs.err = ctx.dev_error_flags;
-        fs.n_unhandled = n_unhandled;
-        fs.queue = B.counters.as<unsigned>() + (Caps::K + 8 + DYN_COUNT);
-        fs.write_cals = 0;
-        fs.dbg = nullptr;
-        launch_flatten_score(n, st, fs);
-        // S3: a block per read of the job in either launch; the blocks past a list's length leave at once
-        Stage3Args s3;
-        s3.tab.tab = dj.tab;
-        s3.tab.r2i = B.r2i.as<double>();
-        s3.tab.i2r = B.i2r.as<double>();
-        s3.tab.orig = B.orig.as<int32_t>();
-        s3.tab.n_tab = in->n_tab;
-        s3.tab.max_indel_size = in->max_indel_size;
-        s3.tab.consulted = dj.consulted;
-        s3.opt = in->stage3_opt;
-        s3.n_reads = n;
-        s3.status = ea.status;
-        s3.cal_off = fa.cal_off;
-        s3.cals = fa.pool;
-        s3.slot = fa.list;
-        s3.scores = B.scores.as<double>();
-        s3.read_off = fa.read_off;
-        s3.read_code = fa.read_code;
-        s3.map_level = B.map_level.as<int32_t>();
-        s3.order = B.s3_order.as<int32_t>();
-        s3.smooth = B.s3_smooth.as<double>();
-        s3.flag = B.s3_flag.as<uint8_t>();
-        s3.rm_type = B.s3_rm_type.as<uint8_t>();
-        s3.rm_pos = B.s3_rm_pos.as<int32_t>();
-        s3.key = B.s3_key.as<uint32_t>();
-        s3.sorted_score = B.s3_sorted_score.as<double>();
-        s3.sorted_hash = B.s3_sorted_hash.as<uint32_t>();
-        s3.next_same = B.s3_next_same.as<int32_t>();
-        s3.removed = B.s3_removed.as<uint8_t>();
-        s3.range_end = B.s3_range_end.as<int32_t>();
-        s3.out = B.s3_out.as<sk3::Out>();
-        s3.skip_if = n_unhandled;
-        auto lds_bytes = [](const int cals) { return size_t(cals) * (8 + 8 + 4 + 4 + 4 + 4 + 1 + 1) + 8; };
-        s3.list = B.s3_list.as<int32_t>();
-        s3.n_list = dyn + DYN_N_LIGHT;
-        s3.list_step = 1;
-        s3.lds_cals = light_cals;
-        SK_LAUNCH(stage3_kernel<1>, dim3(n), dim3(64), lds_bytes(light_cals), st, s3);
-        s3.list = B.s3_list.as<int32_t>() + (n - 1);
-        s3.n_list = dyn + DYN_N_HEAVY;
-        s3.list_step = -1;
-        s3.lds_cals = lds_cals; // (the largest read of the list is not known here: LDS for the most a block holds)
-        SK_LAUNCH(stage3_kernel<4>, dim3(n), dim3(256), lds_bytes(lds_cals), st, s3);
-        SK_HIP(skrt::getLastError());
-        // the results: the zero arena whole (counters + the scans' numbers, warn, n_raw, status, ..., consulted, cal_off) and stage 3's records
-        if (stage_by_kernel) {
-            const size_t out_bytes = sizeof(sk3::Out) * size_t(n);
-            const uint32_t n_a = uint32_t(zero_bytes / 16), n_b = uint32_t((out_bytes + 15) / 16); // (buffers are reserved with slack)
-            const int blocks = int(std::min<size_t>(std::max<size_t>((std::max(zero_bytes, out_bytes) / 16 + 255) / 256, 1), 256));
-            SK_LAUNCH(job_stage_out_kernel, dim3(blocks), dim3(256), 0, st, static_cast<const uint4*>(B.zero_arena.p), static_cast<uint4*>(B.h_zero_arena.p), n_a,
-                               static_cast<const uint4*>(B.s3_out.p), static_cast<uint4*>(B.h_s3_out.p), n_b);
-            SK_HIP(skrt::getLastError());
-        } else {
-            SK_HIP(skrt::memcpyAsync(B.h_zero_arena.p, B.zero_arena.p, zero_bytes, hipMemcpyDeviceToHost, st));
-            D2H(h_s3_out, s3_out, sizeof(sk3::Out) * size_t(n));
-        }
-        const auto t_submitted = std::chrono::steady_clock::now();
-        SK_HIP(skrt::streamSynchronize(st));
-        const auto t_waited = std::chrono::steady_clock::now();
-        g_job_seconds.setup += std::chrono::duration<double>(t_setup - t_begin).count();
-        g_job_seconds.submit += std::chrono::duration<double>(t_submitted - t_setup).count();
-        g_job_seconds.wait += std::chrono::duration<double>(t_waited - t_submitted).count();
-        lap("one sequence");
-        const int32_t* h_counters = B.h_counters.as<int32_t>();
-        if (h_dyn[DYN_FLAGS] != 0 || h_counters[Caps::K + 7] > 0) {
-            if (timing) std::fprintf(stderr, "[enum-dev] one sequence: flags %d, reads outside F5's form %d -> the staged chain\n", h_dyn[DYN_FLAGS], h_counters[Caps::K + 7]);
-            *redo = true;
-            return 0;
-        }
-        ++g_jobs_one_wait;
-        {
-            uint8_t* w8 = reinterpret_cast<uint8_t*>(B.h_warn.p);
-            const int32_t* w32 = B.h_warn.as<int32_t>();
-            for (int r = 0; r < n; ++r) w8[r] = uint8_t(w32[r]);
-            out->warn = w8;
-        }
-        std::memcpy(h_cal_off, B.h_cal_off_z.p, 4 * size_t(n + 1));
-        const int32_t n_cals = h_cal_off[n];
-        g_n_cals = n_cals;
-        g_cals_pool = fa.pool;
-        g_cals_list = fa.list;
-        g_scores = B.scores.as<double>();
-        out->cals = nullptr;   // (in the pool: sk_enum_device_fetch_cals)
-        out->scores = nullptr; // (on the device: sk_enum_device_fetch_scores -- the host needs them only for a read stage 3 turned down)
-        out->stage3 = B.h_s3_out.as<sk3::Out>();
-        out->ref_reads_outside = h_dyn[DYN_REF_OUTSIDE];
-        g_last.fused = true;
-        g_last.fs = fs;
-        g_last.fs.f.n_cals = n_cals;
-        g_last.fs.f.ref_outside = nullptr; // (a repeat for the clock counts nothing)
-        g_last.n = n;
-        g_last.n_cals = n_cals;
-        g_last.scores = B.scores.as<double>();
-        g_last.cells = 0;
-        for (int r = 0; r < n; ++r) g_last.cells += (in->read_off[r + 1] - in->read_off[r]) * int64_t(h_cal_off[r + 1] - h_cal_off[r]);
-        g_last.valid = true;
-        if (timing) std::fprintf(stderr, "[enum-dev] one sequence: %d reads, %d levels launched, %d leaves, %d candidate alignments, stage 3 lists %d + %d\n", n, n_levels,
-                                 h_counters[Caps::K + 3], n_cals, h_dyn[DYN_N_LIGHT], h_dyn[DYN_N_HEAVY]);
-        return 0;
+// E1: the launches of depths [d0, d1) -- depth -1 is the root launch --, the two level buffers taking turns
+void launch_search(const JobPlan& p, EnumArgs ea, const int d0, const int d1, const int level_blocks)
+{
+    PFrame* const buf[2] = { p.B.level_a.as<PFrame>(), p.B.level_b.as<PFrame>() };
+    for (int d = d0; d < d1; ++d) {
+        ea.level_in = (d < 0) ? nullptr : buf[d & 1];
+        ea.level_out = buf[(d + 1) & 1];
+        ea.depth = d;
+        if (d < 0) SK_LAUNCH(root_kernel, dim3((p.n + 63) / 64), dim3(64), 0, p.st, ea);
+        else SK_LAUNCH(level_kernel, dim3(level_blocks), dim3(64), 64 * sizeof(PFrame), p.st, ea);
     }
-    ++g_jobs_staged;
-    {
-        PFrame* buf[2] = { B.level_a.as<PFrame>(), B.level_b.as<PFrame>() };
-        ea.level_in = nullptr;
-        ea.level_out = buf[0];
-        ea.depth = -1;
-        SK_LAUNCH(root_kernel, dim3((n + 63) / 64), dim3(64), 0, st, ea);
-        const size_t lds = 64 * sizeof(PFrame);
-        const int blocks = int(std::min<int64_t>((frame_cap + 63) / 64, 1024));
-        // a call at depth d expands indel order[d]; a call at depth n_order is a leaf.  A read's order as it arrives says how deep its
-        // search goes unless an alignment reaches indels beyond the read's first range (they join the order): the levels up to the
-        // deepest order of the job (+1) go out at once, the level counts that come back with the results say whether more are needed
-        int max_order = 0;
-        for (int r = 0; r < n; ++r) max_order = std::max(max_order, int(in->reads[r].n_order));
-        int done = 0, batch = std::min(std::max(max_order + 2, 3), int(Caps::K) + 2);
-        for (;;) {
-            const int upto = std::min(done + batch, int(Caps::K) + 2);
-            for (int d = done; d < upto; ++d) {
-                ea.level_in = buf[d & 1];
-                ea.level_out = buf[(d + 1) & 1];
-                ea.depth = d;
-                SK_LAUNCH(level_kernel, dim3(blocks), dim3(64), lds, st, ea);
-            }
-            done = upto;
-            SK_HIP(skrt::getLastError());
-            if (fetch_zero(B.counters, B.status, 4 * size_t(n))) return 1; // counters, warn, n_raw, status
-            SK_HIP(skrt::streamSynchronize(st));
-            if (done >= Caps::K + 2 || B.h_counters.as<int32_t>()[done] == 0) break;
-            batch = 4;
-        }
-    }
-    lap("E1 search (all depths)");
-    int32_t* h_status = B.h_status.as<int32_t>();
-    const int32_t* h_counters = B.h_counters.as<int32_t>();
-    const int32_t n_leaves = std::min<int32_t>(h_counters[Caps::K + 3], int32_t(pool_cap));
-    if (timing) {
-        long long calls = 0;
-        int deepest = 0;
-        for (int d = 0; d < Caps::K + 3; ++d) {
-            calls += h_counters[d];
-            if (h_counters[d]) deepest = d;
-        }
-        std::fprintf(stderr, "[enum-dev] search calls %lld, deepest level %d, leaves found %d\n", calls, deepest, n_leaves);
-    }
-    {
-        uint8_t* w8 = reinterpret_cast<uint8_t*>(B.h_warn.p); // (in place: byte r is written after int r was read)
-        const int32_t* w32 = B.h_warn.as<int32_t>();
-        for (int r = 0; r < n; ++r) w8[r] = uint8_t(w32[r]);
-        out->warn = w8;
-    }
+}
 
-    // ---- E2: leaves -> each read's set
-    const int32_t* h_n_raw = B.h_n_raw.as<int32_t>();
-    int32_t* h_raw_off = B.h_raw_off.as<int32_t>();
-    h_raw_off[0] = 0;
-    for (int r = 0; r < n; ++r) h_raw_off[r + 1] = h_raw_off[r] + ((h_status[r] == ST_OK) ? h_n_raw[r] : 0);
-    const int32_t n_grouped = h_raw_off[n];
-    RES(grouped, 4 * size_t(n_grouped));
-    RES(ghash, 4 * size_t(n_grouped));
-    RES(gkey, 16 * size_t(n_grouped));
-    RES(dup, size_t(n_grouped));
-    RES(sorted, 4 * size_t(n_grouped));
-    SetArgs sa;
-    std::memset(&sa, 0, sizeof(sa));
-    sa.pool = ea.pool;
-    sa.leaf_read = ea.leaf_read;
-    sa.leaf_hash = ea.leaf_hash;
-    sa.status = ea.status;
-    sa.n_reads = n;
+// n_leaves_dev: null, or where the search counted its leaves (n_leaves is then the pool's capacity)
+SetArgs set_args(const JobPlan& p, const int32_t n_leaves, const int32_t* n_leaves_dev, const int32_t* cal_off)
+{
+    EnumBuffers& B = p.B;
+    SetArgs sa{};
+    sa.pool = B.pool.as<PCal>();
+    sa.leaf_read = B.leaf_read.as<int32_t>();
+    sa.leaf_hash = B.leaf_hash.as<uint32_t>();
+    sa.status = B.status.as<int32_t>();
+    sa.n_reads = p.n;
     sa.n_leaves = n_leaves;
+    sa.n_leaves_dev = n_leaves_dev;
     sa.raw_off = B.raw_off.as<int32_t>();
     sa.fill = B.fill.as<int32_t>();
     sa.grouped = B.grouped.as<int32_t>();
@@ -2856,340 +2630,555 @@ static int enum_device_run_impl(const SkEnumInput* in, SkEnumOutput* out, const 
     sa.gkey = B.gkey.as<ulonglong2>();
     sa.dup = B.dup.as<uint8_t>();
     sa.n_uniq = B.n_uniq.as<int32_t>();
-    sa.cal_off = B.cal_off.as<int32_t>();
+    sa.cal_off = cal_off;
     sa.sorted = B.sorted.as<int32_t>();
-    sa.n_leaves_dev = nullptr;
-    SK_HIP(skrt::memcpyAsync(B.raw_off.p, h_raw_off, 4 * size_t(n + 1), hipMemcpyHostToDevice, st));
-    if (n_grouped > 0) {
-        SK_LAUNCH(group_kernel, dim3((n_leaves + 255) / 256), dim3(256), 0, st, sa);
-        SK_LAUNCH(dedupe_kernel, dim3((n_grouped + 255) / 256), dim3(256), 0, st, sa);
-        SK_HIP(skrt::getLastError());
-    }
-    if (fetch_zero(B.n_uniq, B.n_uniq, 4 * size_t(n))) return 1;
-    SK_HIP(skrt::streamSynchronize(st));
-    const int32_t* h_n_uniq = B.h_n_uniq.as<int32_t>();
-    for (int r = 0; r < n; ++r) h_cal_off[r + 1] = h_cal_off[r] + ((h_status[r] == ST_OK) ? h_n_uniq[r] : 0);
-    const int32_t n_cals = h_cal_off[n];
-    SK_HIP(skrt::memcpyAsync(B.cal_off.p, h_cal_off, 4 * size_t(n + 1), hipMemcpyHostToDevice, st));
-    if (n_grouped > 0) {
-        SK_LAUNCH(rank_kernel, dim3((n_grouped + 255) / 256), dim3(256), 0, st, sa);
-        SK_HIP(skrt::getLastError());
-    }
-    lap("E2 sets");
+    return sa;
+}
 
-    // ---- L1, L2: layout of the batch
-    RES(n_ops, 4 * size_t(n_cals));
-    RES(op_off, 8 * size_t(n_cals + 1));
-    HRES(h_n_ops, 4 * size_t(n_cals));
-    HRES(h_op_off, 8 * size_t(n_cals + 1));
-    FlatArgs fa;
-    std::memset(&fa, 0, sizeof(fa));
-    fa.job = dj;
+// n_cals_on_device: the count is cal_off[n] (n_cals is then a capacity); n_ops: null unless L2 runs; chain: with the arrays of the
+// staged chain (F1-F3 + A1c), which are reserved once the layout pass has come back
+FlatArgs flat_args(const JobPlan& p, const int32_t n_cals, const bool n_cals_on_device, const int32_t* cal_off, int32_t* n_ops, const bool chain)
+{
+    EnumBuffers& B = p.B;
+    FlatArgs fa{};
+    fa.job = p.dj;
     fa.ins_pool = B.ins.as<char>();
     fa.ref = B.ref.as<char>();
     fa.ref_code = B.ref_code.as<uint8_t>() + F5_CODE_PAD;
     fa.ins_code = B.ins_code.as<uint8_t>();
-    fa.ref_offset = in->ref_offset;
-    fa.ref_len = in->ref_len;
-    fa.n_reads = n;
+    fa.ref_offset = p.in->ref_offset;
+    fa.ref_len = p.in->ref_len;
+    fa.n_reads = p.n;
     fa.n_cals = n_cals;
-    fa.pool = ea.pool;
+    fa.n_cals_on_device = n_cals_on_device ? 1 : 0;
+    fa.pool = B.pool.as<PCal>();
     fa.list = B.sorted.as<int32_t>();
-    fa.status = ea.status;
+    fa.status = B.status.as<int32_t>();
     fa.read_off = B.read_off.as<int64_t>();
     fa.read_code = B.read_code.as<uint8_t>();
-    fa.cal_off = B.cal_off.as<int32_t>();
+    fa.cal_off = cal_off;
     fa.win_begin = B.win_begin.as<int32_t>();
     fa.win_len = B.win_len.as<int32_t>();
     fa.hap_len = B.hap_len.as<int32_t>();
     fa.n_ins = B.n_ins.as<int32_t>();
     fa.ins_idx = B.ins_idx.as<int16_t>();
     fa.ins_off = B.ins_off.as<int32_t>();
-    fa.n_ops = B.n_ops.as<int32_t>();
+    fa.n_ops = n_ops;
     fa.win_end = B.win_end.as<int32_t>();
     fa.ins_lo = B.ins_lo.as<int32_t>();
     fa.ins_hi = B.ins_hi.as<int32_t>();
-    RES(n_seg8, size_t(n_cals));
     fa.n_seg8 = B.n_seg8.as<uint8_t>();
-    fa.ref_outside = B.counters.as<int32_t>() + (Caps::K + 8 + DYN_REF_OUTSIDE);
+    fa.max_read_len = p.in->max_read_len;
+    fa.ref_outside = B.counters.as<int32_t>() + CNT_DYN + DYN_REF_OUTSIDE;
+    if (chain) {
+        fa.cals = B.cals.as<PCal>();
+        fa.hap_off = B.hap_off.as<int64_t>();
+        fa.op_off = B.op_off.as<int64_t>();
+        fa.hap_code = B.hap_code.as<uint8_t>();
+        fa.ops = B.ops.as<sk_score_op>();
+        fa.entries = B.entries.as<uint32_t>();
+        fa.evmask = B.evmask.as<uint32_t>();
+        fa.evmask_words = p.W;
+        fa.colmat = B.colmat.as<uint8_t>();
+        fa.colmat_off = B.colmat_off.as<int64_t>();
+        fa.addmask = B.addmask.as<uint32_t>();
+    }
+    return fa;
+}
+
+FusedScoreArgs fused_args(const JobPlan& p, const FlatArgs& fa)
+{
+    EnumBuffers& B = p.B;
+    FusedScoreArgs fs;
+    fs.f = fa;
+    fs.read_qual = B.read_qual.as<uint8_t>();
+    fs.tab = sk_ctx().dev_tables;
+    fs.scores = B.scores.as<double>();
+    fs.err = sk_ctx().dev_error_flags;
+    fs.n_unhandled = B.counters.as<int32_t>() + CNT_UNHANDLED;
+    fs.queue = B.counters.as<unsigned>() + CNT_QUEUE;
+    fs.write_cals = 0;
+    fs.dbg = nullptr;
+    return fs;
+}
+
+// stage 3's arrays: per candidate alignment (n_cals: the count, or a capacity), per base, a record per read
+int reserve_stage3(EnumBuffers& B, const int n, const int64_t n_bases, const int32_t n_cals)
+{
+    if (reserve_dev({ { B.s3_order, 4 * size_t(n_cals) }, { B.s3_smooth, 8 * size_t(n_cals) }, { B.s3_flag, size_t(n_cals) },
+                      { B.s3_rm_type, size_t(n_bases) }, { B.s3_rm_pos, 4 * size_t(n_bases) }, { B.s3_key, 16 * size_t(n_cals) },
+                      { B.s3_sorted_score, 8 * size_t(n_cals) }, { B.s3_sorted_hash, 4 * size_t(n_cals) }, { B.s3_next_same, 4 * size_t(n_cals) },
+                      { B.s3_removed, size_t(n_cals) }, { B.s3_range_end, 4 * size_t(n_cals) }, { B.s3_out, sizeof(sk3::Out) * size_t(n) } }))
+        return 1;
+    return reserve_pinned({ { B.h_s3_out, sizeof(sk3::Out) * size_t(n) } });
+}
+
+// cals, slot: the records in set order and null -- or the pool the search left its leaves in and each alignment's slot there;
+// skip_if: null, or F5's count of the reads it turned down (nothing runs when it is not zero: the scores are incomplete).
+// What is a launch's own (its list, the capacity in LDS) is launch_stage3's
+Stage3Args stage3_args(const JobPlan& p, const FlatArgs& fa, const PCal* cals, const int32_t* slot, const int32_t* skip_if)
+{
+    EnumBuffers& B = p.B;
+    Stage3Args s3{};
+    s3.tab.tab = p.dj.tab;
+    s3.tab.r2i = B.r2i.as<double>();
+    s3.tab.i2r = B.i2r.as<double>();
+    s3.tab.orig = B.orig.as<int32_t>();
+    s3.tab.n_tab = p.in->n_tab;
+    s3.tab.max_indel_size = p.in->max_indel_size;
+    s3.tab.consulted = p.dj.consulted;
+    s3.opt = p.in->stage3_opt;
+    s3.n_reads = p.n;
+    s3.status = fa.status;
+    s3.cal_off = fa.cal_off;
+    s3.cals = cals;
+    s3.slot = slot;
+    s3.scores = B.scores.as<double>();
+    s3.read_off = fa.read_off;
+    s3.read_code = fa.read_code;
+    s3.map_level = B.map_level.as<int32_t>();
+    s3.order = B.s3_order.as<int32_t>();
+    s3.smooth = B.s3_smooth.as<double>();
+    s3.flag = B.s3_flag.as<uint8_t>();
+    s3.rm_type = B.s3_rm_type.as<uint8_t>();
+    s3.rm_pos = B.s3_rm_pos.as<int32_t>();
+    s3.key = B.s3_key.as<uint32_t>();
+    s3.sorted_score = B.s3_sorted_score.as<double>();
+    s3.sorted_hash = B.s3_sorted_hash.as<uint32_t>();
+    s3.next_same = B.s3_next_same.as<int32_t>();
+    s3.removed = B.s3_removed.as<uint8_t>();
+    s3.range_end = B.s3_range_end.as<int32_t>();
+    s3.out = B.s3_out.as<sk3::Out>();
+    s3.skip_if = skip_if;
+    return s3;
+}
+
+// one of stage 3's two launches, WAVES wavefronts a read: `blocks` reads of `list` (n_list null), or a block per read of the job with the
+// list's length on the device (n_list; list_step -1: the list is filled from the back)
+template <int WAVES>
+void launch_stage3(hipStream_t st, Stage3Args s3, const int blocks, const int32_t* list, const int32_t* n_list, const int list_step, const int lds_cals)
+{
+    s3.list = list;
+    s3.n_list = n_list;
+    s3.list_step = list_step;
+    s3.lds_cals = lds_cals;
+    SK_LAUNCH(stage3_kernel<WAVES>, dim3(blocks), dim3(64 * WAVES), size_t(lds_cals) * (8 + 8 + 4 + 4 + 4 + 4 + 1 + 1) + 8, st, s3);
+}
+
+// warn as the caller reads it: a byte per read, made in place (byte r is written after int r was read)
+const uint8_t* narrow_warn(EnumBuffers& B, const int n)
+{
+    uint8_t* w8 = reinterpret_cast<uint8_t*>(B.h_warn.p);
+    const int32_t* w32 = B.h_warn.as<int32_t>();
+    for (int r = 0; r < n; ++r) w8[r] = uint8_t(w32[r]);
+    return w8;
+}
+
+// ---- what sk_enum_device_rescore replays
+int64_t job_cells(const SkEnumInput* in, const int32_t* h_cal_off)
+{
+    int64_t cells = 0;
+    for (int r = 0; r < in->n_reads; ++r) cells += (in->read_off[r + 1] - in->read_off[r]) * int64_t(h_cal_off[r + 1] - h_cal_off[r]);
+    return cells;
+}
+void remember_fused(const JobPlan& p, const FusedScoreArgs& fs, const int32_t n_cals)
+{
+    g_last.fused = true;
+    g_last.fs = fs;
+    g_last.fs.f.n_cals = n_cals;       // (the count, where the run knew a capacity)
+    g_last.fs.f.ref_outside = nullptr; // (a repeat for the clock counts nothing)
+    g_last.n = p.n;
+    g_last.n_cals = n_cals;
+    g_last.scores = fs.scores;
+    g_last.cells = job_cells(p.in, p.B.h_cal_off.as<int32_t>());
+    g_last.valid = true;
+}
+void remember_staged(const JobPlan& p, const FlatArgs& fa, const sk_align_batch& d, const size_t colmat_bytes)
+{
+    g_last.fused = false;
+    g_last.fa = fa;
+    g_last.fa.ref_outside = nullptr;
+    g_last.d = d;
+    g_last.mask_bytes = p.mask_bytes;
+    g_last.colmat_bytes = colmat_bytes;
+    g_last.n = p.n;
+    g_last.n_cals = fa.n_cals;
+    g_last.scores = p.B.scores.as<double>();
+    g_last.cells = job_cells(p.in, p.B.h_cal_off.as<int32_t>());
+    g_last.valid = true;
+}
+
+// ---- the job as one fixed sequence: ~20 submissions, no host decision between them, ONE wait.  Everything the host computes between the
+// staged run's waits is computed by job_scan_kernel; every buffer is sized by a capacity known now; launches whose size the host does
+// not know cover the capacity with a grid-stride loop (or a block per read of the job that leaves at once).
+// *redo is set when the sequence's assumptions did not hold for this job and nothing of `out` is valid: the caller runs it again the staged way
+int run_one_wait(const JobPlan& p, SkEnumOutput* out, bool* redo)
+{
+    const auto t_setup = std::chrono::steady_clock::now();
+    EnumBuffers& B = p.B;
+    hipStream_t st = p.st;
+    const int n = p.n;
+    const int32_t n_cap = int32_t(p.pool_cap); // leaves, grouped leaves and candidate alignments are all at most this many
+    if (reserve_dev({ { B.grouped, 4 * size_t(n_cap) }, { B.ghash, 4 * size_t(n_cap) }, { B.gkey, 16 * size_t(n_cap) }, { B.dup, size_t(n_cap) },
+                      { B.sorted, 4 * size_t(n_cap) }, { B.n_seg8, size_t(n_cap) }, { B.scores, 8 * size_t(n_cap) }, { B.s3_list, 4 * size_t(n) } }) ||
+        reserve_stage3(B, n, p.n_bases, n_cap))
+        return 1;
+    int32_t* const dyn = B.counters.as<int32_t>() + CNT_DYN;
+
+    // E1: root + the levels up to the deepest order of the job (+ 2: indels that join an order on the way); whether calls were left
+    // for a deeper level is looked at on the device (scan 1) and reported with the results
+    const EnumArgs ea = enum_args(p, true);
+    int n_levels = std::min(p.max_order + 3, int(SEARCH_LEVELS));
+    if (const char* e = std::getenv("SK_ENUM_TEST_LEVELS")) // tests: too few levels, so that the device reports it and the job runs again
+        if (std::atoi(e) > 0) n_levels = std::min(n_levels, std::atoi(e));
+    // (a level of this job has at most a few frames per read: blocks beyond that would only read the count and leave)
+    launch_search(p, ea, -1, n_levels, int(std::min<int64_t>(std::min<int64_t>((p.frame_cap + 63) / 64, 1024), std::max<int64_t>(n, 16))));
+    // scan 1: raw_off
+    ScanArgs sc{};
+    sc.n_reads = n;
+    sc.status = ea.status;
+    sc.count = ea.n_raw;
+    sc.off = B.raw_off.as<int32_t>();
+    sc.dyn = dyn;
+    sc.level_count = ea.level_count;
+    sc.first_level_not_launched = (n_levels >= SEARCH_LEVELS) ? -1 : n_levels;
+    sc.n_leaves = ea.n_leaves;
+    sc.pool_cap = n_cap;
+    SK_LAUNCH(job_scan_kernel<false>, dim3(1), dim3(1024), 0, st, sc);
+    // E2
+    const SetArgs sa = set_args(p, n_cap, ea.n_leaves, B.cal_off_z.as<int32_t>());
+    // (grids for counts the host has not seen: enough blocks for ~64 leaves per read, the loops cover the rest)
+    const int e2_blocks = int(std::min<int64_t>(std::max<int64_t>((int64_t(n) * 64 + 255) / 256, 8), 2048));
+    SK_LAUNCH(group_kernel, dim3(e2_blocks), dim3(256), 0, st, sa);
+    SK_LAUNCH(dedupe_kernel, dim3(e2_blocks), dim3(256), 0, st, sa);
+    // scan 2: cal_off, stage 3's lists
+    sc.count = B.n_uniq.as<int32_t>();
+    sc.off = B.cal_off_z.as<int32_t>();
+    sc.list = B.s3_list.as<int32_t>();
+    sc.light_cals = p.light_cals;
+    SK_LAUNCH(job_scan_kernel<true>, dim3(1), dim3(1024), 0, st, sc);
+    SK_LAUNCH(rank_kernel, dim3(e2_blocks), dim3(256), 0, st, sa);
+    // L1
+    const FlatArgs fa = flat_args(p, n_cap, true, B.cal_off_z.as<int32_t>(), nullptr, false);
+    SK_LAUNCH(pool_bounds_kernel, dim3(e2_blocks), dim3(256), 0, st, fa);
+    SK_LAUNCH(pool_layout_kernel, dim3((n + 63) / 64), dim3(64), 0, st, fa);
+    // F5
+    const FusedScoreArgs fs = fused_args(p, fa);
+    launch_flatten_score(n, st, fs);
+    // S3: a block per read of the job in either launch; the blocks past a list's length leave at once
+    // (the largest read of the heavy list is not known here: LDS for the most a block holds)
+    const Stage3Args s3 = stage3_args(p, fa, fa.pool, fa.list, fs.n_unhandled);
+    launch_stage3<1>(st, s3, n, B.s3_list.as<int32_t>(), dyn + DYN_N_LIGHT, 1, p.light_cals);
+    launch_stage3<4>(st, s3, n, B.s3_list.as<int32_t>() + (n - 1), dyn + DYN_N_HEAVY, -1, p.lds_cals);
+    SK_HIP(skrt::getLastError());
+    // the results: the zero arena whole (counters + the scans' numbers, warn, n_raw, status, ..., consulted, cal_off) and stage 3's records
+    const size_t out_bytes = sizeof(sk3::Out) * size_t(n);
+    if (stage_by_kernel()) {
+        const uint32_t n_a = uint32_t(p.zero_bytes / 16), n_b = uint32_t((out_bytes + 15) / 16); // (buffers are reserved with slack)
+        const int blocks = int(std::min<size_t>(std::max<size_t>((std::max(p.zero_bytes, out_bytes) / 16 + 255) / 256, 1), 256));
+        SK_LAUNCH(job_stage_out_kernel, dim3(blocks), dim3(256), 0, st, static_cast<const uint4*>(B.zero_arena.p), static_cast<uint4*>(B.h_zero_arena.p), n_a,
+                  static_cast<const uint4*>(B.s3_out.p), static_cast<uint4*>(B.h_s3_out.p), n_b);
+        SK_HIP(skrt::getLastError());
+    } else {
+        if (copy_down(st, B.h_zero_arena, B.zero_arena, p.zero_bytes) || copy_down(st, B.h_s3_out, B.s3_out, out_bytes)) return 1;
+    }
+    const auto t_submitted = std::chrono::steady_clock::now();
+    SK_HIP(skrt::streamSynchronize(st));
+    const auto t_waited = std::chrono::steady_clock::now();
+    g_job_seconds.setup += std::chrono::duration<double>(t_setup - p.t_begin).count();
+    g_job_seconds.submit += std::chrono::duration<double>(t_submitted - t_setup).count();
+    g_job_seconds.wait += std::chrono::duration<double>(t_waited - t_submitted).count();
+    p.lap("one sequence");
+    const int32_t* h_counters = B.h_counters.as<int32_t>();
+    const int32_t* const h_dyn = h_counters + CNT_DYN;
+    if (h_dyn[DYN_FLAGS] != 0 || h_counters[CNT_UNHANDLED] > 0) {
+        if (p.timing)
+            std::fprintf(stderr, "[enum-dev] one sequence: flags %d, reads outside F5's form %d -> the staged chain\n", h_dyn[DYN_FLAGS], h_counters[CNT_UNHANDLED]);
+        *redo = true;
+        return 0;
+    }
+    ++g_jobs_one_wait;
+    out->warn = narrow_warn(B, n);
+    int32_t* h_cal_off = B.h_cal_off.as<int32_t>();
+    std::memcpy(h_cal_off, B.h_cal_off_z.p, 4 * size_t(n + 1));
+    const int32_t n_cals = h_cal_off[n];
+    g_n_cals = n_cals;
+    g_cals_pool = fa.pool;
+    g_cals_list = fa.list;
+    g_scores = B.scores.as<double>();
+    out->cals = nullptr;   // (in the pool: sk_enum_device_fetch_cals)
+    out->scores = nullptr; // (on the device: sk_enum_device_fetch_scores -- the host needs them only for a read stage 3 turned down)
+    out->stage3 = B.h_s3_out.as<sk3::Out>();
+    out->ref_reads_outside = h_dyn[DYN_REF_OUTSIDE];
+    remember_fused(p, fs, n_cals);
+    if (p.timing)
+        std::fprintf(stderr, "[enum-dev] one sequence: %d reads, %d levels launched, %d leaves, %d candidate alignments, stage 3 lists %d + %d\n", n, n_levels,
+                     h_counters[CNT_LEAVES], n_cals, h_dyn[DYN_N_LIGHT], h_dyn[DYN_N_HEAVY]);
+    return 0;
+}
+
+// ---- the staged run
+
+// what follows the scores in either chain: the scores' way back, stage 3 (lists made here: the host has the counts).  cals_in_set_order:
+// the staged chain left the records in B.cals (flatten_kernel); else they are where the search put them, and F5 counted the reads it turned
+// down: stage 3 then has nothing to work on -- the staged chain scores the job and this runs again
+int after_scores(const JobPlan& p, SkEnumOutput* out, const FlatArgs& fa, const bool cals_in_set_order)
+{
+    EnumBuffers& B = p.B;
+    hipStream_t st = p.st;
+    const int n = p.n;
+    if (copy_down(st, B.h_scores, B.scores, 8 * size_t(fa.n_cals))) return 1;
+    out->scores = B.h_scores.as<double>();
+    if (!p.in->want_stage3) return 0;
+    if (reserve_stage3(B, n, p.n_bases, fa.n_cals)) return 1;
+    const Stage3Args s3 = cals_in_set_order ? stage3_args(p, fa, fa.cals, nullptr, nullptr)
+                                            : stage3_args(p, fa, fa.pool, fa.list, B.counters.as<int32_t>() + CNT_UNHANDLED);
+    // two launches: reads with few candidate alignments (small LDS, many wavefronts per CU) and the others
+    if (reserve_dev({ { B.s3_list, 4 * size_t(n) } }) || reserve_pinned({ { B.h_s3_list, 4 * size_t(n) } })) return 1;
+    int32_t* h_list = B.h_s3_list.as<int32_t>();
+    const int32_t* h_cal_off = B.h_cal_off.as<int32_t>();
+    int n_light = 0, n_heavy = 0, max_cals = 0;
+    for (int r = 0; r < n; ++r) {
+        const int k = h_cal_off[r + 1] - h_cal_off[r];
+        if (k <= p.light_cals) h_list[n_light++] = r;
+        else {
+            h_list[n - 1 - n_heavy++] = r;
+            max_cals = std::max(max_cals, k);
+        }
+    }
+    if (copy_up(st, B.s3_list, h_list, 4 * size_t(n))) return 1;
+    if (n_light > 0) launch_stage3<1>(st, s3, n_light, B.s3_list.as<int32_t>(), nullptr, 1, p.light_cals);
+    if (n_heavy > 0) {
+        const int32_t* heavy = B.s3_list.as<int32_t>() + (n - n_heavy);
+        const int lds_cals = std::min(max_cals, p.lds_cals); // (a read with more uses the arrays in HBM)
+        // four wavefronts per read: the loops over the read's alignments go four times as wide, lane 0's share stays
+        static const bool one_wave = std::getenv("SK_STAGE3_ONE_WAVE") != nullptr; // (diagnostics)
+        if (one_wave) launch_stage3<1>(st, s3, n_heavy, heavy, nullptr, 1, lds_cals);
+        else launch_stage3<4>(st, s3, n_heavy, heavy, nullptr, 1, lds_cals);
+    }
+    if (p.timing)
+        std::fprintf(stderr, "[enum-dev] stage 3: %d reads with at most %d candidate alignments, %d with more (up to %d)\n", n_light, p.light_cals, n_heavy, max_cals);
+    SK_HIP(skrt::getLastError());
+    if (copy_down(st, B.h_s3_out, B.s3_out, sizeof(sk3::Out) * size_t(n))) return 1;
+    out->stage3 = B.h_s3_out.as<sk3::Out>();
+    p.lap("S3 stage 3");
+    return 0;
+}
+
+// the staged chain's flattening and scoring (L2, F1-F3, A1c: ops, entries, column words through HBM) and, with scores, what follows them.
+// It leaves the records in set order in B.cals.  layout: the job's FlatArgs as L1 ran with them
+int run_chain(const JobPlan& p, SkEnumOutput* out, const FlatArgs& layout)
+{
+    const SkEnumInput* in = p.in;
+    EnumBuffers& B = p.B;
+    hipStream_t st = p.st;
+    const int n = p.n;
+    const int32_t n_cals = layout.n_cals;
+    const int32_t* h_status = B.h_status.as<int32_t>();
+    const int32_t* h_cal_off = B.h_cal_off.as<int32_t>();
+    if (reserve_dev({ { B.cals, sizeof(PCal) * size_t(n_cals) } })) return 1;
+    g_cals_gathered = true; // (flatten_kernel below writes them)
+    if (n_cals > 0) {
+        SK_LAUNCH(op_count_kernel, dim3((n_cals + 63) / 64), dim3(64), 0, st, layout);
+        SK_HIP(skrt::getLastError());
+    }
+    if (fetch_zero(p, B.status, B.hap_len, 4 * size_t(n))) return 1; // status, hap_len (the host has made bytes of its copy of warn)
+    if (copy_down(st, B.h_n_ops, B.n_ops, 4 * size_t(n_cals))) return 1;
+    SK_HIP(skrt::streamSynchronize(st));
+    p.lap("L1+L2 layout");
+
+    const int32_t* h_hap_len = B.h_hap_len.as<int32_t>();
+    const int32_t* h_n_ops = B.h_n_ops.as<int32_t>();
+    int64_t* h_hap_off = B.h_hap_off.as<int64_t>();
+    int64_t* h_op_off = B.h_op_off.as<int64_t>();
+    h_hap_off[0] = 0;
+    h_op_off[0] = 0;
+    int32_t max_hap = 1;
+    for (int r = 0; r < n; ++r) {
+        const int32_t c0 = h_cal_off[r], c1 = h_cal_off[r + 1];
+        h_hap_off[r + 1] = h_hap_off[r] + ((c1 > c0) ? h_hap_len[r] : 0);
+        if (c1 > c0) max_hap = std::max(max_hap, h_hap_len[r]);
+        const bool ok = (h_status[r] == ST_OK); // (a read turned down by L1/L2 keeps its slots in the batch, with no ops)
+        for (int32_t c = c0; c < c1; ++c) h_op_off[c + 1] = h_op_off[c] + (ok ? h_n_ops[c] : 0);
+    }
+    const int64_t n_hap = h_hap_off[n], ops_total = h_op_off[n_cals];
+
+    if (reserve_dev({ { B.hap_code, size_t(n_hap) + 16 }, { B.ops, sizeof(sk_score_op) * size_t(ops_total) }, { B.entries, 4 * (size_t(ops_total) + 2 * size_t(n_cals) + 1) } }) ||
+        reserve_pinned({ { B.h_colmat_off, 8 * size_t(n + 1) } }))
+        return 1;
+    int64_t* h_colmat_off = B.h_colmat_off.as<int64_t>();
+    h_colmat_off[0] = 0;
+    for (int r = 0; r < n; ++r)
+        h_colmat_off[r + 1] = h_colmat_off[r] + ((in->read_off[r + 1] - in->read_off[r] + 7) / 8) * int64_t(h_cal_off[r + 1] - h_cal_off[r]);
+    const size_t colmat_bytes = 4 * size_t(h_colmat_off[n]) + 16;
+    if (reserve_dev({ { B.colmat, colmat_bytes }, { B.colmat_off, 8 * size_t(n + 1) } })) return 1;
+    if (n_cals == 0) return 0;
+
+    if (copy_up(st, B.hap_off, h_hap_off, 8 * size_t(n + 1)) || copy_up(st, B.op_off, h_op_off, 8 * size_t(n_cals + 1))) return 1;
+    SK_HIP(skrt::memsetAsync(B.mask_arena.p, 0, p.mask_bytes, st)); // evmask, addmask
+    SK_HIP(skrt::memsetAsync(B.colmat.p, SK_SEL_NONE | (SK_SEL_NONE << 4), colmat_bytes, st));
+    if (copy_up(st, B.colmat_off, h_colmat_off, 8 * size_t(n + 1))) return 1;
+    const FlatArgs fa = flat_args(p, n_cals, false, layout.cal_off, layout.n_ops, true);
+    SK_LAUNCH(pool_fill_kernel, dim3(n), dim3(64), 0, st, fa);
+    SK_LAUNCH(flatten_kernel, dim3((n_cals + 63) / 64), dim3(64), 0, st, fa);
+    SK_HIP(skrt::getLastError());
+    if (p.with_stage3) out->cals = nullptr; // (they stay here: sk_enum_device_fetch_cals)
+    else if (copy_down(st, B.h_cals, B.cals, sizeof(PCal) * size_t(n_cals))) return 1;
+    if (!in->want_scores) return 0;
+    // F3: a wave per read ($SK_F3_KERNEL = thread pins the thread-per-alignment form; the tests run both)
+    const bool f3_thread = (std::getenv("SK_F3_KERNEL") != nullptr && std::strcmp(std::getenv("SK_F3_KERNEL"), "thread") == 0);
+    if (f3_thread) SK_LAUNCH(entries_kernel, dim3((n_cals + 63) / 64), dim3(64), 0, st, fa);
+    else SK_LAUNCH(entries_wave_kernel, dim3(n), dim3(64), 0, st, fa);
+    SK_HIP(skrt::getLastError());
+    p.lap("F1-F3 flatten");
+    sk_align_batch d{};
+    d.n_reads = n;
+    d.n_cals = n_cals;
+    d.n_ops = ops_total;
+    d.read_off = B.read_off.as<int64_t>();
+    d.read_code = B.read_code.as<uint8_t>();
+    d.read_qual = B.read_qual.as<uint8_t>();
+    d.hap_off = fa.hap_off;
+    d.hap_code = fa.hap_code;
+    d.cal_off = fa.cal_off;
+    d.op_off = fa.op_off;
+    d.ops = fa.ops;
+    d.max_read_len = in->max_read_len;
+    d.max_hap_len = max_hap;
+    d.entries = fa.entries;
+    d.evmask = fa.evmask;
+    d.evmask_words = p.W;
+    d.colmat = B.colmat.as<uint32_t>();
+    d.colmat_off = fa.colmat_off;
+    d.addmask = fa.addmask;
+    if (sk_score_alignments_launch_hostleg(&d, B.scores.as<double>(), st)) return 1;
+    p.lap("A1 score");
+    remember_staged(p, fa, d, colmat_bytes);
+    return after_scores(p, out, fa, true);
+}
+
+// a wait after the search, one after the sets and one at the end; buffers sized by the counts that came back.  The scores come from F5
+// or, when the job holds a read F5 turns down, when the host wants the alignments without scores and with $SK_A5_FUSED=0 (tests: both
+// chains), from the staged chain
+int run_staged(const JobPlan& p, SkEnumOutput* out)
+{
+    const SkEnumInput* in = p.in;
+    EnumBuffers& B = p.B;
+    hipStream_t st = p.st;
+    const int n = p.n;
+    ++g_jobs_staged;
+    // ---- E1: the search, one launch per depth.  A call at depth d expands indel order[d]; a call at depth n_order is a leaf.  A read's
+    // order as it arrives says how deep its search goes unless an alignment reaches indels beyond the read's first range (they join the
+    // order): the levels up to the deepest order of the job (+1) go out at once, the level counts that come back with the results say
+    // whether more are needed
+    const EnumArgs ea = enum_args(p, false);
+    const int level_blocks = int(std::min<int64_t>((p.frame_cap + 63) / 64, 1024));
+    launch_search(p, ea, -1, 0, level_blocks);
+    for (int done = 0, batch = std::min(std::max(p.max_order + 2, 3), int(SEARCH_LEVELS));; batch = 4) {
+        const int upto = std::min(done + batch, int(SEARCH_LEVELS));
+        launch_search(p, ea, done, upto, level_blocks);
+        done = upto;
+        SK_HIP(skrt::getLastError());
+        if (fetch_zero(p, B.counters, B.status, 4 * size_t(n))) return 1; // counters, warn, n_raw, status
+        SK_HIP(skrt::streamSynchronize(st));
+        if (done >= SEARCH_LEVELS || B.h_counters.as<int32_t>()[CNT_LEVELS + done] == 0) break;
+    }
+    p.lap("E1 search (all depths)");
+    const int32_t* h_status = B.h_status.as<int32_t>();
+    const int32_t* h_counters = B.h_counters.as<int32_t>();
+    const int32_t n_leaves = std::min<int32_t>(h_counters[CNT_LEAVES], int32_t(p.pool_cap));
+    if (p.timing) {
+        long long calls = 0;
+        int deepest = 0;
+        for (int d = 0; d <= SEARCH_LEVELS; ++d) {
+            calls += h_counters[CNT_LEVELS + d];
+            if (h_counters[CNT_LEVELS + d]) deepest = d;
+        }
+        std::fprintf(stderr, "[enum-dev] search calls %lld, deepest level %d, leaves found %d\n", calls, deepest, n_leaves);
+    }
+    out->warn = narrow_warn(B, n);
+
+    // ---- E2: leaves -> each read's set
+    const int32_t* h_n_raw = B.h_n_raw.as<int32_t>();
+    int32_t* h_raw_off = B.h_raw_off.as<int32_t>();
+    h_raw_off[0] = 0;
+    for (int r = 0; r < n; ++r) h_raw_off[r + 1] = h_raw_off[r] + ((h_status[r] == ST_OK) ? h_n_raw[r] : 0);
+    const int32_t n_grouped = h_raw_off[n];
+    if (reserve_dev({ { B.grouped, 4 * size_t(n_grouped) }, { B.ghash, 4 * size_t(n_grouped) }, { B.gkey, 16 * size_t(n_grouped) }, { B.dup, size_t(n_grouped) },
+                      { B.sorted, 4 * size_t(n_grouped) } }))
+        return 1;
+    const SetArgs sa = set_args(p, n_leaves, nullptr, B.cal_off.as<int32_t>());
+    if (copy_up(st, B.raw_off, h_raw_off, 4 * size_t(n + 1))) return 1;
+    if (n_grouped > 0) {
+        SK_LAUNCH(group_kernel, dim3((n_leaves + 255) / 256), dim3(256), 0, st, sa);
+        SK_LAUNCH(dedupe_kernel, dim3((n_grouped + 255) / 256), dim3(256), 0, st, sa);
+        SK_HIP(skrt::getLastError());
+    }
+    if (fetch_zero(p, B.n_uniq, B.n_uniq, 4 * size_t(n))) return 1;
+    SK_HIP(skrt::streamSynchronize(st));
+    const int32_t* h_n_uniq = B.h_n_uniq.as<int32_t>();
+    int32_t* h_cal_off = B.h_cal_off.as<int32_t>();
+    for (int r = 0; r < n; ++r) h_cal_off[r + 1] = h_cal_off[r] + ((h_status[r] == ST_OK) ? h_n_uniq[r] : 0);
+    const int32_t n_cals = h_cal_off[n];
+    if (copy_up(st, B.cal_off, h_cal_off, 4 * size_t(n + 1))) return 1;
+    if (n_grouped > 0) {
+        SK_LAUNCH(rank_kernel, dim3((n_grouped + 255) / 256), dim3(256), 0, st, sa);
+        SK_HIP(skrt::getLastError());
+    }
+    p.lap("E2 sets");
+
+    // ---- L1: layout of the batch
+    if (reserve_dev({ { B.n_ops, 4 * size_t(n_cals) }, { B.op_off, 8 * size_t(n_cals + 1) }, { B.n_seg8, size_t(n_cals) }, { B.scores, 8 * size_t(n_cals) } }) ||
+        reserve_pinned({ { B.h_n_ops, 4 * size_t(n_cals) }, { B.h_op_off, 8 * size_t(n_cals + 1) }, { B.h_scores, 8 * size_t(n_cals) } }))
+        return 1;
+    if (!p.with_stage3 && reserve_pinned({ { B.h_cals, sizeof(PCal) * size_t(n_cals) } })) return 1;
+    const FlatArgs fa = flat_args(p, n_cals, false, B.cal_off.as<int32_t>(), B.n_ops.as<int32_t>(), false);
     // (byte patterns: 0x7f7f7f7f is large enough to stand for "no lower bound yet", 0x80808080 is below any position / index)
-    SK_HIP(skrt::memsetAsync(B.minmax_arena.p, 0x7f, minmax_p[2].off, st));                               // win_begin, ins_lo
-    SK_HIP(skrt::memsetAsync(static_cast<char*>(B.minmax_arena.p) + minmax_p[2].off, 0x80, minmax_bytes - minmax_p[2].off, st)); // win_end, ins_hi
+    SK_HIP(skrt::memsetAsync(B.minmax_arena.p, 0x7f, p.minmax_split, st));                                                                // win_begin, ins_lo
+    SK_HIP(skrt::memsetAsync(static_cast<char*>(B.minmax_arena.p) + p.minmax_split, 0x80, p.minmax_bytes - p.minmax_split, st)); // win_end, ins_hi
     if (n_cals > 0) SK_LAUNCH(pool_bounds_kernel, dim3((n_cals + 255) / 256), dim3(256), 0, st, fa);
     SK_LAUNCH(pool_layout_kernel, dim3((n + 63) / 64), dim3(64), 0, st, fa);
     SK_HIP(skrt::getLastError());
-    // ---- flattening + scoring.  The default is F5 (flatten_score_kernel): one launch from the records to the scores, no layout pass
-    // and no host wait before stage 3.  F1-F3 + A1c (the staged chain: ops, entries, column words through HBM) run when the job
-    // holds a read F5 turns down, when the host wants the alignments without scores, and with $SK_A5_FUSED=0 (tests: both chains).
-    const bool fused_enabled = !(std::getenv("SK_A5_FUSED") != nullptr && std::strcmp(std::getenv("SK_A5_FUSED"), "0") == 0);
-    const bool try_fused = fused_enabled && in->want_scores && n_cals > 0;
-    RES(scores, 8 * size_t(n_cals));
-    if (!(in->want_scores && in->want_stage3)) HRES(h_cals, sizeof(PCal) * size_t(n_cals));
-    HRES(h_scores, 8 * size_t(n_cals));
     out->cals = B.h_cals.as<PCal>();
     g_n_cals = n_cals;
-    fa.max_read_len = in->max_read_len;
     g_cals_pool = fa.pool;
     g_cals_list = fa.list;
-    bool cals_in_set_order = false; // F5 reads the records where the search left them; the staged chain copies them (flatten_kernel)
 
-    // what follows the scores in either chain: bookkeeping for sk_enum_device_rescore, the scores' way back, stage 3
-    auto after_scores = [&]() -> int {
-        D2H(h_scores, scores, 8 * size_t(n_cals));
-        out->scores = B.h_scores.as<double>();
-        if (in->want_stage3) {
-            RES(s3_order, 4 * size_t(n_cals));
-            RES(s3_smooth, 8 * size_t(n_cals));
-            RES(s3_flag, size_t(n_cals));
-            RES(s3_rm_type, size_t(n_bases));
-            RES(s3_rm_pos, 4 * size_t(n_bases));
-            RES(s3_key, 16 * size_t(n_cals));
-            RES(s3_sorted_score, 8 * size_t(n_cals));
-            RES(s3_sorted_hash, 4 * size_t(n_cals));
-            RES(s3_next_same, 4 * size_t(n_cals));
-            RES(s3_removed, size_t(n_cals));
-            RES(s3_range_end, 4 * size_t(n_cals));
-            RES(s3_out, sizeof(sk3::Out) * size_t(n));
-            HRES(h_s3_out, sizeof(sk3::Out) * size_t(n));
-            Stage3Args s3;
-            s3.tab.tab = dj.tab;
-            s3.tab.r2i = B.r2i.as<double>();
-            s3.tab.i2r = B.i2r.as<double>();
-            s3.tab.orig = B.orig.as<int32_t>();
-            s3.tab.n_tab = in->n_tab;
-            s3.tab.max_indel_size = in->max_indel_size;
-            s3.tab.consulted = dj.consulted;
-            s3.opt = in->stage3_opt;
-            s3.n_reads = n;
-            s3.status = ea.status;
-            s3.cal_off = fa.cal_off;
-            s3.cals = cals_in_set_order ? fa.cals : fa.pool;
-        s3.slot = cals_in_set_order ? nullptr : fa.list;
-            s3.scores = B.scores.as<double>();
-            s3.read_off = fa.read_off;
-            s3.read_code = fa.read_code;
-            s3.map_level = B.map_level.as<int32_t>();
-            s3.order = B.s3_order.as<int32_t>();
-            s3.smooth = B.s3_smooth.as<double>();
-            s3.flag = B.s3_flag.as<uint8_t>();
-            s3.rm_type = B.s3_rm_type.as<uint8_t>();
-            s3.rm_pos = B.s3_rm_pos.as<int32_t>();
-            s3.key = B.s3_key.as<uint32_t>();
-            s3.sorted_score = B.s3_sorted_score.as<double>();
-            s3.sorted_hash = B.s3_sorted_hash.as<uint32_t>();
-            s3.next_same = B.s3_next_same.as<int32_t>();
-            s3.removed = B.s3_removed.as<uint8_t>();
-            s3.range_end = B.s3_range_end.as<int32_t>();
-            s3.out = B.s3_out.as<sk3::Out>();
-            s3.n_list = nullptr;
-            s3.list_step = 1;
-            // (F5 counts the reads it turns down: stage 3 then has nothing to work on -- the staged chain scores the job and calls this again)
-            s3.skip_if = cals_in_set_order ? nullptr : (B.counters.as<int32_t>() + (Caps::K + 7));
-            // two launches: reads with few candidate alignments (small LDS, many wavefronts per CU) and the others
-            RES(s3_list, 4 * size_t(n));
-            HRES(h_s3_list, 4 * size_t(n));
-            int32_t* h_list = B.h_s3_list.as<int32_t>();
-            int light_cals = S3_LIGHT_CALS, lds_cals = S3_LDS_CALS;
-            if (const char* e = std::getenv("SK_STAGE3_TEST_LDS_CALS")) { // tests: small capacities, so that the second launch and the HBM arrays run
-                int a = 0, b = 0;
-                if (std::sscanf(e, "%d,%d", &a, &b) == 2 && a > 0 && b >= a && b <= S3_LDS_CALS) {
-                    light_cals = a;
-                    lds_cals = b;
-                }
-            }
-            int n_light = 0, n_heavy = 0, max_cals = 0;
-            for (int r = 0; r < n; ++r) {
-                const int k = h_cal_off[r + 1] - h_cal_off[r];
-                if (k <= light_cals) h_list[n_light++] = r;
-                else {
-                    h_list[n - 1 - n_heavy++] = r;
-                    max_cals = std::max(max_cals, k);
-                }
-            }
-            H2D(s3_list, h_list, 4 * size_t(n));
-            auto lds_bytes = [](const int cals) { return size_t(cals) * (8 + 8 + 4 + 4 + 4 + 4 + 1 + 1) + 8; };
-            if (n_light > 0) {
-                s3.list = B.s3_list.as<int32_t>();
-                s3.lds_cals = light_cals;
-                SK_LAUNCH(stage3_kernel<1>, dim3(n_light), dim3(64), lds_bytes(light_cals), st, s3);
-            }
-            if (n_heavy > 0) {
-                s3.list = B.s3_list.as<int32_t>() + (n - n_heavy);
-                s3.lds_cals = std::min(max_cals, lds_cals); // (a read with more uses the arrays in HBM)
-                // four wavefronts per read: the loops over the read's alignments go four times as wide, lane 0's share stays
-                static const bool one_wave = std::getenv("SK_STAGE3_ONE_WAVE") != nullptr; // (diagnostics)
-                if (one_wave) SK_LAUNCH(stage3_kernel<1>, dim3(n_heavy), dim3(64), lds_bytes(s3.lds_cals), st, s3);
-                else SK_LAUNCH(stage3_kernel<4>, dim3(n_heavy), dim3(256), lds_bytes(s3.lds_cals), st, s3);
-            }
-            if (timing) std::fprintf(stderr, "[enum-dev] stage 3: %d reads with at most %d candidate alignments, %d with more (up to %d)\n", n_light, light_cals, n_heavy, max_cals);
-            SK_HIP(skrt::getLastError());
-            D2H(h_s3_out, s3_out, sizeof(sk3::Out) * size_t(n));
-            out->stage3 = B.h_s3_out.as<sk3::Out>();
-            lap("S3 stage 3");
-        }
-        return 0;
-    };
-
-    bool staged = !try_fused;
-    if (try_fused) {
-        FusedScoreArgs fs;
-        fs.f = fa;
-        fs.read_qual = B.read_qual.as<uint8_t>();
-        fs.tab = ctx.dev_tables;
-        fs.scores = B.scores.as<double>();
-        fs.err = ctx.dev_error_flags;
-        fs.n_unhandled = B.counters.as<int32_t>() + (Caps::K + 7);
-        fs.queue = B.counters.as<unsigned>() + (Caps::K + 8 + DYN_COUNT);
-        fs.write_cals = 0;
-        fs.dbg = nullptr;
+    // ---- flattening + scoring.  The default is F5 (flatten_score_kernel): one launch from the records to the scores, no layout pass
+    // and no host wait before stage 3; it reads the records where the search left them
+    const bool fused_enabled = !(std::getenv("SK_A5_FUSED") != nullptr && std::strcmp(std::getenv("SK_A5_FUSED"), "0") == 0);
+    bool chain = !(fused_enabled && in->want_scores && n_cals > 0);
+    if (!chain) {
+        const FusedScoreArgs fs = fused_args(p, fa);
         launch_flatten_score(n, st, fs);
         SK_HIP(skrt::getLastError());
-        lap("F5 flatten + score");
+        p.lap("F5 flatten + score");
         if (in->want_stage3) {
             out->cals = nullptr; // (they stay here, in the pool: sk_enum_device_fetch_cals gathers them when the host asks)
         } else {
-            RES(cals, sizeof(PCal) * size_t(n_cals));
+            if (reserve_dev({ { B.cals, sizeof(PCal) * size_t(n_cals) } })) return 1;
             SK_LAUNCH(gather_cals_kernel, dim3((n_cals + 63) / 64), dim3(64), 0, st, fa.pool, fa.list, n_cals, B.cals.as<PCal>());
             SK_HIP(skrt::getLastError());
             g_cals_gathered = true;
-            D2H(h_cals, cals, sizeof(PCal) * size_t(n_cals));
+            if (copy_down(st, B.h_cals, B.cals, sizeof(PCal) * size_t(n_cals))) return 1;
         }
-        g_last.fused = true;
-        g_last.fs = fs;
-        g_last.fs.f.ref_outside = nullptr; // (a repeat for the clock counts nothing)
-        g_last.n = n;
-        g_last.n_cals = n_cals;
-        g_last.scores = B.scores.as<double>();
-        g_last.cells = 0;
-        for (int r = 0; r < n; ++r) g_last.cells += (in->read_off[r + 1] - in->read_off[r]) * int64_t(h_cal_off[r + 1] - h_cal_off[r]);
-        g_last.valid = true;
-        if (after_scores()) return 1;
-        if (fetch_zero(B.counters, B.counters, 4 * size_t(n_counters))) return 1; // (n_unhandled)
-        if (fetch_zero(B.status, B.status, 4 * size_t(n))) return 1;               // (F5 may have turned reads down: ST_FAIL)
+        remember_fused(p, fs, n_cals);
+        if (after_scores(p, out, fa, false)) return 1;
+        if (fetch_zero(p, B.counters, B.counters, 4 * size_t(N_COUNTERS))) return 1; // (n_unhandled)
+        if (fetch_zero(p, B.status, B.status, 4 * size_t(n))) return 1;             // (F5 may have turned reads down: ST_FAIL)
         SK_HIP(skrt::streamSynchronize(st));
-        if (B.h_counters.as<int32_t>()[Caps::K + 7] > 0) staged = true; // a read outside F5's form: the staged chain over the job
+        chain = B.h_counters.as<int32_t>()[CNT_UNHANDLED] > 0; // a read outside F5's form: the staged chain over the job
     }
-    if (staged) {
-        RES(cals, sizeof(PCal) * size_t(n_cals));
-        fa.cals = B.cals.as<PCal>();
-        cals_in_set_order = true;
-        g_cals_gathered = true; // (flatten_kernel below writes them)
-        if (n_cals > 0) {
-            SK_LAUNCH(op_count_kernel, dim3((n_cals + 63) / 64), dim3(64), 0, st, fa);
-            SK_HIP(skrt::getLastError());
-        }
-        if (fetch_zero(B.status, B.hap_len, 4 * size_t(n))) return 1; // status, hap_len (the host has made bytes of its copy of warn)
-        D2H(h_n_ops, n_ops, 4 * size_t(n_cals));
-        SK_HIP(skrt::streamSynchronize(st));
-        lap("L1+L2 layout");
-
-        const int32_t* h_hap_len = B.h_hap_len.as<int32_t>();
-        const int32_t* h_n_ops = B.h_n_ops.as<int32_t>();
-        int64_t* h_hap_off = B.h_hap_off.as<int64_t>();
-        int64_t* h_op_off = B.h_op_off.as<int64_t>();
-        h_hap_off[0] = 0;
-        h_op_off[0] = 0;
-        int32_t max_hap = 1;
-        for (int r = 0; r < n; ++r) {
-            const int32_t c0 = h_cal_off[r], c1 = h_cal_off[r + 1];
-            h_hap_off[r + 1] = h_hap_off[r] + ((c1 > c0) ? h_hap_len[r] : 0);
-            if (c1 > c0) max_hap = std::max(max_hap, h_hap_len[r]);
-            const bool ok = (h_status[r] == ST_OK); // (a read turned down by L1/L2 keeps its slots in the batch, with no ops)
-            for (int32_t c = c0; c < c1; ++c) h_op_off[c + 1] = h_op_off[c] + (ok ? h_n_ops[c] : 0);
-        }
-        const int64_t n_hap = h_hap_off[n], ops_total = h_op_off[n_cals];
-
-        RES(hap_code, size_t(n_hap) + 16);
-        RES(ops, sizeof(sk_score_op) * size_t(ops_total));
-        RES(entries, 4 * (size_t(ops_total) + 2 * size_t(n_cals) + 1));
-        HRES(h_colmat_off, 8 * size_t(n + 1));
-        int64_t* h_colmat_off = B.h_colmat_off.as<int64_t>();
-        h_colmat_off[0] = 0;
-        for (int r = 0; r < n; ++r)
-            h_colmat_off[r + 1] = h_colmat_off[r] + ((in->read_off[r + 1] - in->read_off[r] + 7) / 8) * int64_t(h_cal_off[r + 1] - h_cal_off[r]);
-        const int64_t colmat_words = h_colmat_off[n];
-        RES(colmat, 4 * size_t(colmat_words) + 16);
-        RES(colmat_off, 8 * size_t(n + 1));
-
-        if (n_cals > 0) {
-            SK_HIP(skrt::memcpyAsync(B.hap_off.p, h_hap_off, 8 * size_t(n + 1), hipMemcpyHostToDevice, st));
-            SK_HIP(skrt::memcpyAsync(B.op_off.p, h_op_off, 8 * size_t(n_cals + 1), hipMemcpyHostToDevice, st));
-            SK_HIP(skrt::memsetAsync(B.mask_arena.p, 0, mask_bytes, st)); // evmask, addmask
-            SK_HIP(skrt::memsetAsync(B.colmat.p, SK_SEL_NONE | (SK_SEL_NONE << 4), 4 * size_t(colmat_words) + 16, st));
-            SK_HIP(skrt::memcpyAsync(B.colmat_off.p, h_colmat_off, 8 * size_t(n + 1), hipMemcpyHostToDevice, st));
-            fa.hap_off = B.hap_off.as<int64_t>();
-            fa.op_off = B.op_off.as<int64_t>();
-            fa.hap_code = B.hap_code.as<uint8_t>();
-            fa.ops = B.ops.as<sk_score_op>();
-            fa.entries = B.entries.as<uint32_t>();
-            fa.evmask = B.evmask.as<uint32_t>();
-            fa.evmask_words = W;
-            fa.colmat = B.colmat.as<uint8_t>();
-            fa.colmat_off = B.colmat_off.as<int64_t>();
-            fa.addmask = B.addmask.as<uint32_t>();
-            SK_LAUNCH(pool_fill_kernel, dim3(n), dim3(64), 0, st, fa);
-            SK_LAUNCH(flatten_kernel, dim3((n_cals + 63) / 64), dim3(64), 0, st, fa);
-            SK_HIP(skrt::getLastError());
-            if (in->want_scores && in->want_stage3) out->cals = nullptr; // (they stay here: sk_enum_device_fetch_cals)
-            else D2H(h_cals, cals, sizeof(PCal) * size_t(n_cals));
-            if (in->want_scores) {
-                // F3: a wave per read ($SK_F3_KERNEL = thread pins the thread-per-alignment form; the tests run both)
-                const bool f3_thread = (std::getenv("SK_F3_KERNEL") != nullptr && std::strcmp(std::getenv("SK_F3_KERNEL"), "thread") == 0);
-                if (f3_thread) SK_LAUNCH(entries_kernel, dim3((n_cals + 63) / 64), dim3(64), 0, st, fa);
-                else SK_LAUNCH(entries_wave_kernel, dim3(n), dim3(64), 0, st, fa);
-                SK_HIP(skrt::getLastError());
-                lap("F1-F3 flatten");
-                sk_align_batch d;
-                std::memset(&d, 0, sizeof(d));
-                d.n_reads = n;
-                d.n_cals = n_cals;
-                d.n_ops = ops_total;
-                d.read_off = B.read_off.as<int64_t>();
-                d.read_code = B.read_code.as<uint8_t>();
-                d.read_qual = B.read_qual.as<uint8_t>();
-                d.hap_off = fa.hap_off;
-                d.hap_code = fa.hap_code;
-                d.cal_off = fa.cal_off;
-                d.op_off = fa.op_off;
-                d.ops = fa.ops;
-                d.max_read_len = in->max_read_len;
-                d.max_hap_len = max_hap;
-                d.entries = fa.entries;
-                d.evmask = fa.evmask;
-                d.evmask_words = W;
-                d.colmat = B.colmat.as<uint32_t>();
-                d.colmat_off = fa.colmat_off;
-                d.addmask = fa.addmask;
-                if (sk_score_alignments_launch_hostleg(&d, B.scores.as<double>(), st)) return 1;
-                lap("A1 score");
-                g_last.fused = false;
-                g_last.fa = fa;
-                g_last.fa.ref_outside = nullptr;
-                g_last.d = d;
-                g_last.n = n;
-                g_last.n_cals = n_cals;
-                g_last.mask_bytes = mask_bytes;
-                g_last.colmat_bytes = 4 * size_t(colmat_words) + 16;
-                g_last.scores = B.scores.as<double>();
-                g_last.cells = 0;
-                for (int r = 0; r < n; ++r) g_last.cells += (in->read_off[r + 1] - in->read_off[r]) * int64_t(h_cal_off[r + 1] - h_cal_off[r]);
-                g_last.valid = true;
-                if (after_scores()) return 1;
-            }
-        }
-    }
-    if (fetch_zero(B.consulted, B.consulted, size_t(in->n_tab))) return 1;
-    if (fetch_zero(B.counters, B.counters, 4 * size_t(n_counters))) return 1;
+    if (chain && run_chain(p, out, fa)) return 1;
+    if (fetch_zero(p, B.consulted, B.consulted, size_t(in->n_tab))) return 1;
+    if (fetch_zero(p, B.counters, B.counters, 4 * size_t(N_COUNTERS))) return 1;
     SK_HIP(skrt::streamSynchronize(st));
     // (when F5 turned a read down both chains filled the pools: the count may be double -- what matters to the caller is zero or not)
-    out->ref_reads_outside = B.h_counters.as<int32_t>()[Caps::K + 8 + DYN_REF_OUTSIDE];
-    lap("done");
-#undef RES
-#undef HRES
-#undef H2D
-#undef D2H
+    out->ref_reads_outside = B.h_counters.as<int32_t>()[CNT_DYN + DYN_REF_OUTSIDE];
+    p.lap("done");
     return 0;
 }
+} // namespace
 
 // A job with the whole read path on the device (scores + stage 3) and F5 enabled runs as one fixed sequence with one wait; a job for
 // which the sequence's assumptions do not hold (reported by the device with the results), one too large for capacity-sized buffers, and
@@ -3199,14 +3188,72 @@ extern "C" int sk_enum_device_run(const SkEnumInput* in, SkEnumOutput* out)
 {
     const bool enabled = !(std::getenv("SK_ENUM_ONE_WAIT") != nullptr && std::strcmp(std::getenv("SK_ENUM_ONE_WAIT"), "0") == 0);
     const bool fused_enabled = !(std::getenv("SK_A5_FUSED") != nullptr && std::strcmp(std::getenv("SK_A5_FUSED"), "0") == 0);
-    bool redo = false;
     if (enabled && fused_enabled && in && in->want_scores && in->want_stage3 && in->n_reads > 0 && in->n_reads <= ONE_WAIT_MAX_READS &&
         in->max_read_len <= F5_MAX_READ) {
-        const int rc = enum_device_run_impl(in, out, true, &redo);
+        JobPlan p;
+        bool redo = false;
+        const int rc = start_job(in, out, true, p) || run_one_wait(p, out, &redo);
         if (rc != 0 || !redo) return rc;
         ++g_jobs_one_wait_redone;
     }
-    return enum_device_run_impl(in, out, false, &redo);
+    JobPlan p; // (a job run again is prepared again from the start: a new generation, another layout of the zero arena)
+    if (start_job(in, out, false, p)) return 1;
+    return p.n == 0 ? 0 : run_staged(p, out);
+}
+
+// diagnostics ($SK_F5_TIMING): where a wave of F5 spends its cycles on the last run's job, and how the kernel's time grows with the grid
+static int f5_timing_report(hipStream_t st)
+{
+    FusedScoreArgs fs = g_last.fs;
+    const size_t nb = size_t(g_last.n) * F5_STAMPS;
+    unsigned long long* d = nullptr;
+    SK_HIP(skrt::malloc_(reinterpret_cast<void**>(&d), nb * 8));
+    SK_HIP(skrt::memsetAsync(d, 0, nb * 8, st));
+    fs.dbg = d;
+    launch_flatten_score(g_last.n, st, fs);
+    std::vector<unsigned long long> h(nb);
+    SK_HIP(skrt::memcpyAsync(h.data(), d, nb * 8, hipMemcpyDeviceToHost, st));
+    SK_HIP(skrt::streamSynchronize(st));
+    (void)skrt::free_(d);
+    double sum[F5_STAMPS] = { 0 };
+    unsigned long long first = ~0ull, last = 0;
+    int nblk = 0, ndrawn = 0;
+    for (int r = 0; r < g_last.n; ++r) {
+        const unsigned long long* s = &h[size_t(r) * F5_STAMPS];
+        if (s[6] == 0) continue;
+        ++nblk;
+        first = std::min(first, s[0]);
+        last = std::max(last, s[6]);
+        sum[0] += double(s[1] - s[0]);
+        for (int i = 2; i <= 5; ++i) sum[i] += double(s[i]);
+        sum[7] += double(s[7]);
+        sum[6] += double(s[6] - s[0]);
+        sum[8] += double(s[8]);
+        ndrawn += s[8] != 0;
+    }
+    for (const int grid : { 64, 256, 512, 1024, 1792, 2048, 4096 }) { // how the kernel's time grows with the blocks in flight
+        if (grid > g_last.n) break;
+        hipEvent_t a0, a1;
+        SK_HIP(hipEventCreate(&a0));
+        SK_HIP(hipEventCreate(&a1));
+        FusedScoreArgs f2 = g_last.fs;
+        launch_flatten_score(grid, st, f2);
+        SK_HIP(hipEventRecord(a0, st));
+        for (int k = 0; k < 5; ++k) launch_flatten_score(grid, st, f2);
+        SK_HIP(hipEventRecord(a1, st));
+        SK_HIP(hipEventSynchronize(a1));
+        float ms = 0;
+        SK_HIP(hipEventElapsedTime(&ms, a0, a1));
+        std::fprintf(stderr, "[f5-timing] grid %d blocks: %.1f us per launch\n", grid, ms * 1000.f / 5.f);
+        (void)hipEventDestroy(a0);
+        (void)hipEventDestroy(a1);
+    }
+    if (nblk)
+        std::fprintf(stderr, "[f5-timing] blocks %d: cycles per block: draw %.0f (%d drawn: %.0f each) prologue %.0f staging %.0f phaseA %.0f (walk %.0f) phaseB %.0f total %.0f = %.1f us by the 100 MHz counter (%.0f MHz); kernel span %llu cycles => %.1f blocks in flight\n",
+                     nblk, sum[8] / nblk, ndrawn, sum[8] / std::max(1, ndrawn), sum[0] / nblk, sum[2] / nblk, sum[4] / nblk, sum[7] / nblk, sum[5] / nblk, sum[6] / nblk, sum[3] / nblk / 100.0,
+                     sum[6] / std::max(1.0, sum[3]) * 100.0, last - first,
+                     sum[6] / double(last - first));
+    return 0;
 }
 
 // Measurement entry (bench.py's a5 leg): flattening AND scoring of the candidate alignments the last run left on the device, the way
@@ -3229,57 +3276,7 @@ extern "C" int sk_enum_device_rescore(const int32_t reps, float* out_ms, int32_t
     SK_HIP(hipEventCreate(&e0));
     SK_HIP(hipEventCreate(&e1));
     SK_HIP(hipEventRecord(e0, st));
-    if (g_last.fused && std::getenv("SK_F5_TIMING")) { // diagnostics: where a wave of F5 spends its cycles
-        FusedScoreArgs fs = g_last.fs;
-        const size_t nb = size_t(g_last.n) * F5_STAMPS;
-        unsigned long long* d = nullptr;
-        SK_HIP(skrt::malloc_(reinterpret_cast<void**>(&d), nb * 8));
-        SK_HIP(skrt::memsetAsync(d, 0, nb * 8, st));
-        fs.dbg = d;
-        launch_flatten_score(g_last.n, st, fs);
-        std::vector<unsigned long long> h(nb);
-        SK_HIP(skrt::memcpyAsync(h.data(), d, nb * 8, hipMemcpyDeviceToHost, st));
-        SK_HIP(skrt::streamSynchronize(st));
-        (void)skrt::free_(d);
-        double sum[F5_STAMPS] = { 0 };
-        unsigned long long first = ~0ull, last = 0;
-        int nblk = 0, ndrawn = 0;
-        for (int r = 0; r < g_last.n; ++r) {
-            const unsigned long long* s = &h[size_t(r) * F5_STAMPS];
-            if (s[6] == 0) continue;
-            ++nblk;
-            first = std::min(first, s[0]);
-            last = std::max(last, s[6]);
-            sum[0] += double(s[1] - s[0]);
-            for (int i = 2; i <= 5; ++i) sum[i] += double(s[i]);
-            sum[7] += double(s[7]);
-            sum[6] += double(s[6] - s[0]);
-            sum[8] += double(s[8]);
-            ndrawn += s[8] != 0;
-        }
-        for (const int grid : { 64, 256, 512, 1024, 1792, 2048, 4096 }) { // how the kernel's time grows with the blocks in flight
-            if (grid > g_last.n) break;
-            hipEvent_t a0, a1;
-            SK_HIP(hipEventCreate(&a0));
-            SK_HIP(hipEventCreate(&a1));
-            FusedScoreArgs f2 = g_last.fs;
-            launch_flatten_score(grid, st, f2);
-            SK_HIP(hipEventRecord(a0, st));
-            for (int k = 0; k < 5; ++k) launch_flatten_score(grid, st, f2);
-            SK_HIP(hipEventRecord(a1, st));
-            SK_HIP(hipEventSynchronize(a1));
-            float ms = 0;
-            SK_HIP(hipEventElapsedTime(&ms, a0, a1));
-            std::fprintf(stderr, "[f5-timing] grid %d blocks: %.1f us per launch\n", grid, ms * 1000.f / 5.f);
-            (void)hipEventDestroy(a0);
-            (void)hipEventDestroy(a1);
-        }
-        if (nblk)
-            std::fprintf(stderr, "[f5-timing] blocks %d: cycles per block: draw %.0f (%d drawn: %.0f each) prologue %.0f staging %.0f phaseA %.0f (walk %.0f) phaseB %.0f total %.0f = %.1f us by the 100 MHz counter (%.0f MHz); kernel span %llu cycles => %.1f blocks in flight\n",
-                         nblk, sum[8] / nblk, ndrawn, sum[8] / std::max(1, ndrawn), sum[0] / nblk, sum[2] / nblk, sum[4] / nblk, sum[7] / nblk, sum[5] / nblk, sum[6] / nblk, sum[3] / nblk / 100.0,
-                         sum[6] / std::max(1.0, sum[3]) * 100.0, last - first,
-                         sum[6] / double(last - first));
-    }
+    if (g_last.fused && std::getenv("SK_F5_TIMING") && f5_timing_report(st)) return 1;
     for (int i = 0; i < reps; ++i) {
         if (g_last.fused) { // F5: the records -> the scores in one launch
             launch_flatten_score(g_last.n, st, g_last.fs);

@@ -179,6 +179,42 @@ def test_device_enumeration_equals_host(seed, max_indels, hap, chain, monkeypatc
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("chain", ["fused", "staged"])
+def test_device_scores_with_stage3_on_the_host(chain, monkeypatch):
+    """scores wanted, stage 3 left to the host ($SK_STAGE3_DEVICE=0): the job runs the staged way, the records (after F5: gathered from
+    the pool into set order) and the scores are copied back, and the host's stage 3 works on them -- results equal to the host path's"""
+    capi.init(0)
+    monkeypatch.setenv("SK_STAGE3_DEVICE", "0")
+    monkeypatch.setenv("SK_A5_FUSED", "0" if chain == "staged" else "1")
+    scs = synth.realign_scenarios(12, np.random.default_rng(91555), reads_per=10, max_indels=9, haplotyping_rate=0.3)
+    before = capi.RealignJob.device_job_counts()
+    n_dev = n_s3 = 0
+    for sc in scs:
+        res, cons = {}, {}
+        for mode in (0, 2):
+            job = capi.RealignJob(capi.realign_options(is_haplotyping_enabled=sc["is_haplotyping_enabled"],
+                                                       min_read_bp_flank=sc["min_read_bp_flank"], enumeration=mode))
+            job.set_reference(sc["ref_seq"], sc["ref_offset"])
+            job.set_indels(sc["indels"])
+            idx = T._add_reads(job, sc)
+            job.run()
+            res[mode] = [None if i is None else job.result(i) for i in idx]
+            cons[mode] = job.indels_consulted()
+            if mode == 2:
+                n_dev += job.enumeration_counts()[1]
+                n_s3 += job.stage3_counts()[1]
+        for a, b in zip(res[0], res[2]):
+            assert (a is None) == (b is None)
+            if a is None:
+                continue
+            assert repr(a) == repr(b)
+        assert np.array_equal(cons[0], cons[2])
+    one_wait, redone, staged = (b - a for a, b in zip(before, capi.RealignJob.device_job_counts()))
+    assert n_dev > 50 and n_s3 == 0
+    assert one_wait == 0 and staged > 0
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("kernel", ["thread", "wave"])
 def test_device_flatten_kernels_on_long_reads(kernel, monkeypatch):
     """F3 in both forms ($SK_F3_KERNEL: a thread per candidate alignment / a wave per read with the base comparisons made once per
