@@ -113,6 +113,16 @@ int sk_debug_force_device_libm(int on);
  *  ids_twice != 0 makes the kernel add a repeated key's haplotype id twice, so that a key both alternates carry adds up to more than 3
  *  (SK_ALLELE_DECLINE_ID_SUM).  Both 0 (the state of a fresh process) is the reference's behaviour; nothing else sets them. */
 void sk_debug_region_alleles(int no_edge_deletion, int ids_twice);
+/** Test hook: the order in which the candidate-alignment scoring kernel of the device read path (flatten_score_kernel) takes the last
+ *  reads of a launch, as its table kernel builds it on the device.  cal_off[n_reads + 1]: the reads' offsets into the job's candidate
+ *  alignments; waves: the waves W of the launch's grid; shift: the places s a read moves up per round (64 candidate alignments) beyond
+ *  its first.  Writes the window's first hand-out to *first, its length T = min(n_reads, W + 6 s) to *n and the T reads in hand-out
+ *  order to order_out (room for T entries).  *n = 0 and no launch when n_reads <= waves or shift <= 0: what a job run does then.
+ *  Needs sk_init; 0 on success. */
+int sk_debug_f5_tail_order(const int32_t* cal_off, int32_t n_reads, int32_t waves, int32_t shift, int32_t* first, int32_t* n, int32_t* order_out);
+/** Test hook: how often the device read path's job runs of this process have launched that table kernel (a job that fits the grid, or
+ *  one run with $SK_F5_TAIL_SHIFT=0, launches none). */
+int64_t sk_debug_f5_tail_launches(void);
 
 /** Host copies of the q-score tables the kernels use (71 entries each, Q0..Q70; L/blt_util/qscore_cache.hh:66-68). */
 int sk_get_qscore_tables(double* q2p, double* q2lncompe, double* q2lne);

@@ -245,7 +245,7 @@ EXPORTS = [
     "sk_realign_options_default", "sk_realign_job_create", "sk_realign_job_destroy", "sk_realign_job_error",
     "sk_realign_job_set_reference", "sk_realign_job_set_indels", "sk_realign_job_add_read", "sk_realign_job_add_reads", "sk_realign_job_get_batch",
     "sk_realign_job_finish", "sk_realign_job_run", "sk_realign_job_n_reads", "sk_realign_job_read_result",
-    "sk_realign_job_clear_reads", "sk_realign_job_rescore", "sk_realign_job_indels_consulted", "sk_realign_job_enumeration_counts", "sk_realign_device_job_counts", "sk_realign_reference_reads_outside", "sk_realign_job_stage3_counts", "sk_make_start_pos_alignment", "sk_get_end_pin_start_pos",
+    "sk_realign_job_clear_reads", "sk_realign_job_rescore", "sk_realign_job_indels_consulted", "sk_realign_job_enumeration_counts", "sk_realign_device_job_counts", "sk_debug_f5_tail_order", "sk_debug_f5_tail_launches", "sk_realign_reference_reads_outside", "sk_realign_job_stage3_counts", "sk_make_start_pos_alignment", "sk_get_end_pin_start_pos",
     "sk_germline_options_default", "sk_dependent_eprob", "sk_dependent_eprob_dev", "sk_site_digt_call",
     "sk_site_digt_call_dev", "sk_site_digt_call_fused", "sk_site_digt_call_fused_dev",
     "sk_somatic_snv_options_default", "sk_somatic_snv_call_batch", "sk_somatic_snv_call_batch_dev",
@@ -298,6 +298,9 @@ def lib():
         L.sk_realign_job_enumeration_counts.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
         L.sk_realign_device_job_counts.argtypes = [c_void_p, c_void_p, c_void_p]
         L.sk_realign_device_job_counts.restype = None
+        L.sk_debug_f5_tail_order.argtypes = [c_void_p, C.c_int32, C.c_int32, C.c_int32, c_void_p, c_void_p, c_void_p]
+        L.sk_debug_f5_tail_launches.argtypes = []
+        L.sk_debug_f5_tail_launches.restype = C.c_int64
         L.sk_realign_reference_reads_outside.argtypes = []
         L.sk_realign_reference_reads_outside.restype = C.c_int64
         L.sk_realign_job_stage3_counts.argtypes = [c_void_p, c_void_p, c_void_p]
@@ -1037,6 +1040,23 @@ class RealignJob:
         a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
         lib().sk_realign_device_job_counts(C.byref(a), C.byref(b), C.byref(c))
         return a.value, b.value, c.value
+
+    @staticmethod
+    def f5_tail_launches():
+        """launches of the table kernel of F5's last hand-outs by this process's job runs (sk_debug_f5_tail_launches)"""
+        return int(lib().sk_debug_f5_tail_launches())
+
+    @staticmethod
+    def f5_tail_order(cal_off, waves, shift):
+        """(first, order): the table of F5's last hand-outs as the device builds it for reads with the offsets cal_off[n_reads + 1], a
+        grid of `waves` waves and a shift of `shift` hand-outs per round (sk_debug_f5_tail_order); order is empty when none is built"""
+        cal_off = np.ascontiguousarray(cal_off, np.int32)
+        n_reads = len(cal_off) - 1
+        first, n = C.c_int32(-1), C.c_int32(-1)
+        order = np.full(max(n_reads, 1), -2, np.int32)
+        if lib().sk_debug_f5_tail_order(_p(cal_off), n_reads, int(waves), int(shift), C.byref(first), C.byref(n), _p(order)):
+            raise StrelkaAmdError(last_error())
+        return first.value, order[:n.value].copy()
 
     def stage3_counts(self):
         a, b = C.c_int64(), C.c_int64()

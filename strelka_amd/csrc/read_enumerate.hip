@@ -321,21 +321,22 @@ enum { SEARCH_LEVELS = Caps::K + 2,       // level launches after which no searc
        N_COUNTERS = CNT_QUEUE + 2 };
 static_assert(CNT_LEVELS + SEARCH_LEVELS + 1 == CNT_LEAVES && CNT_NODES > CNT_LEAVES && CNT_NODES + 2 <= CNT_UNHANDLED, "the counters' slots overlap");
 
-__device__ inline int block_exclusive_scan(const int v, int* wave_sums /* LDS [blockDim.x / 64 + 1] */, int* total)
+template <typename V> // (int; unsigned long long: two 32-bit counts scanned as one value, tail_order_kernel)
+__device__ inline V block_exclusive_scan(const V v, V* wave_sums /* LDS [blockDim.x / 64 + 1] */, V* total)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
-    int x = v;
+    V x = v;
     for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, d);
+        const V y = __shfl_up(x, d);
         if (lane >= d) x += y;
     }
     __syncthreads(); // (wave_sums may still be read from a previous scan)
     if (lane == 63) wave_sums[wave] = x;
     __syncthreads();
     if (threadIdx.x == 0) {
-        int run = 0;
+        V run = 0;
         for (int w = 0; w < n_waves; ++w) {
-            const int t = wave_sums[w];
+            const V t = wave_sums[w];
             wave_sums[w] = run;
             run += t;
         }
@@ -863,6 +864,10 @@ struct FusedScoreArgs
     int32_t write_cals;    // the records' copy in set order (stage 3 and sk_enum_device_fetch_cals read it)
     unsigned long long* dbg; // diagnostics ($SK_F5_TIMING): per read F5_STAMPS cycle stamps, or null
     unsigned* queue;       // [2] the launch's read queue: next read, waves that have left (both 0 between launches: the last wave out zeroes them)
+    // the order of the launch's last hand-outs (tail_order_kernel): hand-out h in [tail_first, tail_first + tail_n) is read
+    // tail_order[h - tail_first], every other hand-out h is read h; tail_n = 0: the job's own order throughout
+    const int32_t* tail_order;
+    uint32_t tail_first, tail_n;
 };
 
 // a candidate alignment's slot in LDS: the walk's output -- up to F5_SEGS + 1 transitions, one per op that covers read positions and
@@ -872,7 +877,8 @@ struct FusedScoreArgs
 // goes from 17.8 KB to under 10 KB and a CU holds 16 of them instead of 9 (profiles/r04_a5_history.txt: a wave alone on a CU takes as
 // long as nine sharing it; with sixteen the vector unit is ~85 % busy, profiles/r05_f5_history.txt).
 constexpr int F5_SEGS = 16, F5_INDELS = 8;
-constexpr int F5_STAMPS = 9; // $SK_F5_TIMING: a read's stamps (f5_read; the ninth is the cycles of the draw that handed it out)
+constexpr int F5_STAMPS = 10; // $SK_F5_TIMING: a read's stamps (f5_read; the ninth is the cycles of the draw that handed it out, the
+                              // tenth the 100 MHz counter at the read's start: where the read lies in the launch)
 constexpr int F5_SLOT = (F5_SEGS + 1) | 1; // (odd stride: conflict-free)
 __device__ __forceinline__ int f5_ent_word(const int k) { return k; }
 // doubles per read position: agree, 0.0, differ -- the read's own cases folded in (a '=' base: differ = agree; an N base and the pad
@@ -1614,6 +1620,7 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
         stamp[3] = TIMING ? (unsigned long long)wall_clock64() - wall0 : 0ull;
         stamp[8] = draw_cycles; // the draw that handed this read out, from before the atomic to its value in a scalar register (0: the
                                 // wave's first read, which is not drawn)
+        stamp[9] = wall0;
         for (int i = 0; i < F5_STAMPS; ++i) fa.dbg[size_t(r) * F5_STAMPS + i] = stamp[i];
     }
 }
@@ -1632,9 +1639,10 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
 // gridDim.x * WAVES + the counter's value.  All the grid's waves used to make their first draw on the one word within the ~15 us it takes
 // to place the blocks, and a head word answers ~88 such atomics per us: the last of that burst waited ~45 us for its first read
 // (1.025 -> 0.981 ms, profiles/r09_f5_history.txt; a later draw costs a wave 3 700 - 4 600 cycles at this load, the `draw` figure of
-// $SK_F5_TIMING).  A wave whose number is past the last read leaves without a draw.  The last wave to leave puts the queue back to zero
-// -- every wave counts itself out after its last draw, whether it drew or not -- so that the next launch, the same buffers, the same
-// stream, finds it as this one did.
+// $SK_F5_TIMING).  What is handed out is a number h; it names read h except among the launch's last hand-outs, whose reads are taken
+// from a table in which the reads of several rounds stand earlier than in the job (tail_order_kernel, below).  A wave whose number is
+// past the last read leaves without a draw.  The last wave to leave puts the queue back to zero -- every wave counts itself out after
+// its last draw, whether it drew or not -- so that the next launch, the same buffers, the same stream, finds it as this one did.
 template <int MAXR, bool TIMING, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 4))) void flatten_score_kernel(const FusedScoreArgs fa, const int n_reads)
 {
@@ -1645,9 +1653,14 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 4
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const unsigned n_waves = gridDim.x * unsigned(WAVES);
-    unsigned r = blockIdx.x * unsigned(WAVES) + unsigned(wave); // the first read: the wave's own number, no draw
+    // the first hand-out: the wave's own number, no draw
+    unsigned h = unsigned(__builtin_amdgcn_readfirstlane(int(blockIdx.x * unsigned(WAVES) + unsigned(wave))));
     unsigned long long draw_cycles = 0;
-    while (r < unsigned(n_reads)) {
+    while (h < unsigned(n_reads)) {
+        // hand-out h is read h, except among the launch's last tail_n hand-outs, which go through the table (the same for the whole
+        // wave; one more dependent load, paid by those hand-outs only)
+        unsigned r = h;
+        if (h - fa.tail_first < fa.tail_n) r = unsigned(__builtin_amdgcn_readfirstlane(fa.tail_order[h - fa.tail_first]));
         f5_read<MAXR, TIMING>(fa, int(r), S[wave], q_terms, draw_cycles);
         f5_wave_sync(); // (the wave's LDS object is the next read's)
         const unsigned long long t0 = TIMING ? (unsigned long long)clock64() : 0ull;
@@ -1655,7 +1668,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 4
         if (lane == 0) d = atomicAdd(&fa.queue[0], 1u);
         int drawn = __builtin_amdgcn_readfirstlane(int(d));
         if (TIMING) __asm__ volatile("" : "+s"(drawn)); // (the second stamp stands after the value has arrived)
-        r = n_waves + unsigned(drawn);
+        h = n_waves + unsigned(drawn);
         draw_cycles = TIMING ? (unsigned long long)clock64() - t0 : 0ull;
     }
     if (lane == 0) {
@@ -1670,25 +1683,142 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 4
 // the rows of terms sized for the job's longest read: with 150-base reads a wave's LDS is 10 KB, sixteen waves to a CU (the 256-base
 // form: twelve)
 // eight waves to a block where their LDS leaves room for two blocks to a CU (the short-read form: 76.7 KB), four with the long form
-template <int MAXR, bool TIMING>
-static void launch_flatten_score_t(const int n_reads, hipStream_t st, const FusedScoreArgs& fs)
+// the launch's shape, computed in one place for the launch and for the table of its last hand-outs: the waves of a block and the
+// blocks of the grid.  waves() is W, the reads handed out without a draw.
+struct F5Grid
+{
+    int wpb, blocks;
+    int waves() const { return wpb * blocks; }
+};
+template <int MAXR>
+static F5Grid f5_grid_t(const int n_reads)
 {
     static const int waves = [] { const char* e = std::getenv("SK_F5_WAVES"); return e ? std::atoi(e) : 0; }(); // (experiments: 1, 2, 4, 8, 16; 0 = the default)
     constexpr int DEFAULT_WAVES = (sizeof(F5Lds<MAXR>) * 16 <= 160 * 1024) ? 8 : 4;
     const int w = waves > 0 ? waves : DEFAULT_WAVES;
+    const int wpb = (w == 16 && MAXR <= 152) ? 16 : w >= 8 ? 8 : w == 4 ? 4 : w == 2 ? 2 : 1; // (the instantiations there are)
     // the blocks the device holds at a time (256 CUs; by LDS: 16 waves of the short-read form to a CU, 14 of the long one; a grid larger
     // than that only queues blocks that find the read queue empty, a smaller one leaves slots unused): $SK_F5_GRID = blocks, experiments
     static const int grid_env = [] { const char* e = std::getenv("SK_F5_GRID"); return e ? std::atoi(e) : 0; }();
     constexpr int WAVES_PER_CU = int((160 * 1024) / sizeof(F5Lds<MAXR>)) >= 16 ? 16 : int((160 * 1024) / sizeof(F5Lds<MAXR>));
-    auto grid = [&](const int wpb) {
-        const int resident = grid_env > 0 ? grid_env : 256 * std::max(1, WAVES_PER_CU / wpb);
-        return dim3(unsigned(std::max(1, std::min(resident, (n_reads + wpb - 1) / wpb))));
-    };
-    if (w == 16 && MAXR <= 152) SK_LAUNCH((flatten_score_kernel<152, TIMING, 16>), grid(16), dim3(1024), 0, st, fs, n_reads);
-    else if (w >= 8) SK_LAUNCH((flatten_score_kernel<MAXR, TIMING, 8>), grid(8), dim3(512), 0, st, fs, n_reads);
-    else if (w == 4) SK_LAUNCH((flatten_score_kernel<MAXR, TIMING, 4>), grid(4), dim3(256), 0, st, fs, n_reads);
-    else if (w == 2) SK_LAUNCH((flatten_score_kernel<MAXR, TIMING, 2>), grid(2), dim3(128), 0, st, fs, n_reads);
-    else SK_LAUNCH((flatten_score_kernel<MAXR, TIMING, 1>), grid(1), dim3(64), 0, st, fs, n_reads);
+    const int resident = grid_env > 0 ? grid_env : 256 * std::max(1, WAVES_PER_CU / wpb);
+    return { wpb, std::max(1, std::min(resident, (n_reads + wpb - 1) / wpb)) };
+}
+static F5Grid f5_grid(const int n_reads, const int max_read_len) // (the form launch_flatten_score takes for the job)
+{
+    return max_read_len <= 152 ? f5_grid_t<152>(n_reads) : f5_grid_t<F5_MAX_READ>(n_reads);
+}
+
+template <int MAXR, bool TIMING>
+static void launch_flatten_score_t(const int n_reads, hipStream_t st, const FusedScoreArgs& fs)
+{
+    const F5Grid g = f5_grid_t<MAXR>(n_reads);
+    const dim3 grid(unsigned(g.blocks)), block(unsigned(64 * g.wpb));
+    if (g.wpb == 16) SK_LAUNCH((flatten_score_kernel<152, TIMING, 16>), grid, block, 0, st, fs, n_reads);
+    else if (g.wpb == 8) SK_LAUNCH((flatten_score_kernel<MAXR, TIMING, 8>), grid, block, 0, st, fs, n_reads);
+    else if (g.wpb == 4) SK_LAUNCH((flatten_score_kernel<MAXR, TIMING, 4>), grid, block, 0, st, fs, n_reads);
+    else if (g.wpb == 2) SK_LAUNCH((flatten_score_kernel<MAXR, TIMING, 2>), grid, block, 0, st, fs, n_reads);
+    else SK_LAUNCH((flatten_score_kernel<MAXR, TIMING, 1>), grid, block, 0, st, fs, n_reads);
+}
+
+// ---- the order of the launch's last hand-outs.  A read makes a round per 64 candidate alignments, and a read of four rounds drawn just
+// before the queue runs dry holds the launch open for its whole life while the other waves leave.  The job's order stays as it is (it
+// mixes the kinds of reads: see above) except in a window of the last T = min(n_reads, W + 6 s) hand-outs, W the grid's waves: there a
+// read of c rounds (1-5; a read without candidate alignments counts as 1) moves up by (c - 1) s places -- window position i gets the
+// key i - (c - 1) s, and the window is put in ascending key order, ties to the lower position.  Each kind keeps its own order, nothing
+// is clumped at the launch's start, and the launch's last hand-outs are one-round reads where the window holds enough of them.  No
+// sort is needed: a position's place is the number of positions before it in that order, a sum over the five kinds of counts below an
+// index -- kind q's positions j with j < i + (q - c) s, and j = i + (q - c) s too where q < c.  A block per 1 024 positions.  EVERY block
+// reads the kinds of the whole window (4 bytes a read, a wave 64 consecutive positions, eight loads in flight) and keeps them in LDS as
+// one 64-bit mask per kind 2-5 and 64 positions (kind 1 is the rest), with the kinds' counts before each 64 positions from one
+// block-wide scan of two packed values; a count below an index is then a scan entry plus a population count, and a position looks its
+// five up without leaving the CU.  (As one block that kept the counts per position in HBM the kernel took 77 us for 16 384 positions,
+// a fifth of F5's time on a job of that size: profiles/r10_f5_history.txt.)  No atomics: the table is the same on every run.
+constexpr int F5_TAIL_KINDS = 5;
+constexpr int F5_TAIL_MAX = 65536; // positions of a window: what tail_order_kernel's LDS holds (a larger shift is cut down to fit)
+struct TailArgs
+{
+    const int32_t* cal_off; // [n_reads + 1]
+    int32_t first, n;       // the window: hand-outs [first, first + n), n <= F5_TAIL_MAX
+    int32_t shift;          // s
+    int32_t* order;         // [n] the table: the read of hand-out first + k
+};
+__global__ __launch_bounds__(1024) void tail_order_kernel(const TailArgs a)
+{
+    constexpr int MAX_CHUNKS = F5_TAIL_MAX / 64, AHEAD = 8;
+    __shared__ unsigned long long mask[MAX_CHUNKS + 1][F5_TAIL_KINDS - 1]; // [chunk][q - 2]: the chunk's positions of kind q
+    __shared__ uint4 before[MAX_CHUNKS + 1];                               // the positions of kind 2, 3, 4, 5 before the chunk
+    __shared__ unsigned long long wave_sums[17];
+    const int T = a.n, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int n_chunks = (T + 63) >> 6; // (<= 1 024: a thread a chunk in the scan)
+    for (int c0 = wave; c0 < n_chunks; c0 += 16 * AHEAD) {
+        int lo[AHEAD], hi[AHEAD];
+#pragma unroll
+        for (int u = 0; u < AHEAD; ++u) {
+            const int i = (c0 + 16 * u) * 64 + lane;
+            lo[u] = i < T ? a.cal_off[a.first + i] : 0;
+            hi[u] = i < T ? a.cal_off[a.first + i + 1] : 0;
+        }
+#pragma unroll
+        for (int u = 0; u < AHEAD; ++u) {
+            const int chunk = c0 + 16 * u; // (the same for the wave)
+            if (chunk >= n_chunks) break;
+            const int kind = (chunk * 64 + lane < T) ? min(max((hi[u] - lo[u] + 63) >> 6, 1), F5_TAIL_KINDS) : 0;
+#pragma unroll
+            for (int q = 2; q <= F5_TAIL_KINDS; ++q) {
+                const unsigned long long m = __ballot(kind == q);
+                if (lane == 0) mask[chunk][q - 2] = m;
+            }
+        }
+    }
+    if (t < F5_TAIL_KINDS - 1) mask[n_chunks][t] = 0; // (an index of T itself, where T is a multiple of 64)
+    __syncthreads();
+    unsigned cnt[F5_TAIL_KINDS - 1] = { 0, 0, 0, 0 };
+    if (t < n_chunks) {
+#pragma unroll
+        for (int q = 0; q < F5_TAIL_KINDS - 1; ++q) cnt[q] = unsigned(__popcll(mask[t][q]));
+    }
+    unsigned long long tot23 = 0, tot45 = 0;
+    const unsigned long long at23 = block_exclusive_scan<unsigned long long>(cnt[0] | (unsigned long long)cnt[1] << 32, wave_sums, &tot23);
+    const unsigned long long at45 = block_exclusive_scan<unsigned long long>(cnt[2] | (unsigned long long)cnt[3] << 32, wave_sums, &tot45);
+    if (t < n_chunks) before[t] = make_uint4(unsigned(at23), unsigned(at23 >> 32), unsigned(at45), unsigned(at45 >> 32));
+    if (t == 0) before[n_chunks] = make_uint4(unsigned(tot23), unsigned(tot23 >> 32), unsigned(tot45), unsigned(tot45 >> 32));
+    __syncthreads();
+    for (int i = blockIdx.x * 1024 + t; i < T; i += gridDim.x * 1024) {
+        int c = 1;
+#pragma unroll
+        for (int q = 2; q <= F5_TAIL_KINDS; ++q)
+            if ((mask[i >> 6][q - 2] >> (i & 63)) & 1ull) c = q;
+        int place = 0;
+#pragma unroll
+        for (int q = 1; q <= F5_TAIL_KINDS; ++q) {
+            const long long x = (long long)i + (long long)(q - c) * a.shift + (q < c ? 1 : 0);
+            const int below = int(min(max(x, 0ll), (long long)T)); // kind q's positions [0, below) come before position i
+            const uint4 p = before[below >> 6];
+            const unsigned long long bits = (1ull << (below & 63)) - 1ull;
+            const unsigned long long* const m = mask[below >> 6];
+            const unsigned n2 = p.x + unsigned(__popcll(m[0] & bits)), n3 = p.y + unsigned(__popcll(m[1] & bits));
+            const unsigned n4 = p.z + unsigned(__popcll(m[2] & bits)), n5 = p.w + unsigned(__popcll(m[3] & bits));
+            place += int(q == 1 ? unsigned(below) - (n2 + n3 + n4 + n5) : q == 2 ? n2 : q == 3 ? n3 : q == 4 ? n4 : n5);
+        }
+        if (unsigned(place) < unsigned(T)) a.order[place] = a.first + i; // (a position's place is its own: the order is total)
+    }
+}
+static void launch_tail_order(hipStream_t st, const TailArgs& ta) { SK_LAUNCH(tail_order_kernel, dim3(unsigned(ta.n + 1023) / 1024), dim3(1024), 0, st, ta); }
+// $SK_F5_TAIL_SHIFT = s in hand-outs (experiments and tests; 0 = the job's own order to the end); the default is the grid's waves: of W / 4,
+// W / 2, W, 1.5 W, 2 W and 2.5 W it is the fastest on a job of 65 536 reads and on one of 16 384 (profiles/r10_f5_history.txt: the
+// launch gets shorter up to W and longer again beyond it, as more of the job is put in order of work).  Cut down so that the window fits
+// the table kernel.
+static int f5_tail_shift(const int W)
+{
+    static const int env = [] { const char* e = std::getenv("SK_F5_TAIL_SHIFT"); return e ? std::max(0, std::atoi(e)) : -1; }();
+    return std::min(env >= 0 ? env : W, std::max(0, (F5_TAIL_MAX - W) / 6));
+}
+// the window for a launch over n_reads with W waves: its length T (0: the launch draws nothing, or the shift is off -- no table)
+static int f5_tail_window(const int n_reads, const int W, const int shift)
+{
+    if (n_reads <= W || shift <= 0) return 0;
+    return int(std::min<int64_t>(n_reads, int64_t(W) + 6 * int64_t(shift)));
 }
 
 static void launch_flatten_score(const int n_reads, hipStream_t st, const FusedScoreArgs& fs)
@@ -2223,6 +2353,7 @@ struct EnumBuffers
     DevBuf n_ops, win_len, n_ins, ins_idx, ins_off, n_seg8;
     DevBuf cal_off, hap_off, cals, hap_code, op_off, ops, entries, scores, colmat, colmat_off;
     DevBuf s3_order, s3_smooth, s3_flag, s3_rm_type, s3_rm_pos, s3_key, s3_sorted_score, s3_sorted_hash, s3_next_same, s3_range_end, s3_removed, s3_out, s3_list;
+    DevBuf tail_order; // F5's last hand-outs (tail_order_kernel)
     HostBuf h_s3_out, h_s3_list;
     HostBuf h_raw_off, h_n_ops, h_cal_off, h_hap_off, h_op_off, h_cals, h_scores, h_colmat_off;
 };
@@ -2319,6 +2450,7 @@ namespace
 // statistics of the process: jobs run as one fixed sequence (one wait), and those of them the host ran again the staged way because
 // an assumption of the sequence did not hold (deeper levels than launched, a full leaf pool, a read outside F5's form)
 int64_t g_jobs_one_wait = 0, g_jobs_one_wait_redone = 0, g_jobs_staged = 0;
+int64_t g_tail_launches = 0; // launches of tail_order_kernel by the job drivers (sk_debug_f5_tail_launches)
 // diagnostics ($SK_ENUM_JOB_SECONDS): where a one-sequence job's wall time goes -- buffers + packing, submissions, the wait -- on stderr at exit
 struct JobSeconds
 {
@@ -2337,6 +2469,42 @@ extern "C" void sk_enum_device_job_counts(int64_t* one_wait, int64_t* one_wait_r
     if (one_wait_redone) *one_wait_redone = g_jobs_one_wait_redone;
     if (staged) *staged = g_jobs_staged;
 }
+
+// test hooks (include/strelka_amd.h): the table kernel over a host-given cal_off with the grid's waves and the shift given, in buffers of
+// its own (the last job's stay as they are); and how often the job drivers launched it
+extern "C" int sk_debug_f5_tail_order(const int32_t* cal_off, const int32_t n_reads, const int32_t waves, const int32_t shift, int32_t* first, int32_t* n,
+                                      int32_t* order_out)
+{
+    SK_REQUIRE_INIT();
+    if (!cal_off || n_reads < 0 || waves <= 0 || !first || !n) return sk_fail("sk_debug_f5_tail_order: bad argument");
+    const int T = f5_tail_window(n_reads, waves, shift);
+    *first = T ? n_reads - T : 0;
+    *n = T;
+    if (T == 0) return 0; // (no launch: what the drivers do for such a job)
+    if (T > F5_TAIL_MAX) return sk_fail("sk_debug_f5_tail_order: a window of more than 65536 hand-outs (the drivers cut the shift down)");
+    if (!order_out) return sk_fail("sk_debug_f5_tail_order: no room for the table");
+    SkContext& ctx = sk_ctx();
+    SK_HIP(skrt::setDevice(ctx.device));
+    hipStream_t st = ctx.stream;
+    int32_t *d_off = nullptr, *d_order = nullptr;
+    int rc = 0;
+    auto run = [&]() -> int {
+        SK_HIP(skrt::malloc_(&d_off, 4 * (size_t(n_reads) + 1)));
+        SK_HIP(skrt::malloc_(&d_order, 4 * size_t(T)));
+        SK_HIP(skrt::memcpyAsync(d_off, cal_off, 4 * (size_t(n_reads) + 1), hipMemcpyHostToDevice, st));
+        SK_HIP(skrt::memsetAsync(d_order, 0xff, 4 * size_t(T), st)); // (an entry the kernel left out shows as -1)
+        launch_tail_order(st, TailArgs{ d_off, n_reads - T, T, shift, d_order });
+        SK_HIP(skrt::getLastError());
+        SK_HIP(skrt::memcpyAsync(order_out, d_order, 4 * size_t(T), hipMemcpyDeviceToHost, st));
+        SK_HIP(skrt::streamSynchronize(st));
+        return 0;
+    };
+    rc = run();
+    if (d_off) (void)skrt::free_(d_off);
+    if (d_order) (void)skrt::free_(d_order);
+    return rc;
+}
+extern "C" int64_t sk_debug_f5_tail_launches(void) { return g_tail_launches; }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // the job driver.  A job is prepared once (start_job, plan_job: capacities, the arenas' layout, reservations, the packed input on its way up)
@@ -2429,7 +2597,8 @@ int plan_job(const SkEnumInput* in, const bool one_wait, JobPlan& p)
                       { B.pool, sizeof(PCal) * size_t(p.pool_cap) }, { B.leaf_read, 4 * size_t(p.pool_cap) }, { B.leaf_hash, 4 * size_t(p.pool_cap) },
                       { B.raw_off, 4 * size_t(n + 1) }, { B.win_len, 4 * size_t(n) }, { B.n_ins, 4 * size_t(n) },
                       { B.ins_idx, 2 * size_t(n) * INS_CAP }, { B.ins_off, 4 * size_t(n) * INS_CAP },
-                      { B.cal_off, 4 * size_t(n + 1) }, { B.hap_off, 8 * size_t(n + 1) } }) ||
+                      { B.cal_off, 4 * size_t(n + 1) }, { B.hap_off, 8 * size_t(n + 1) },
+                      { B.tail_order, 4 * size_t(std::min(n, F5_TAIL_MAX)) } }) || // (F5's last hand-outs: a window is at most this, plan_tail)
         reserve_pinned({ { B.h_raw_off, 4 * size_t(n + 1) }, { B.h_cal_off, 4 * size_t(n + 1) }, { B.h_hap_off, 8 * size_t(n + 1) } }))
         return 1;
     // ---- the arenas: pieces at 256-byte offsets
@@ -2699,7 +2868,25 @@ FusedScoreArgs fused_args(const JobPlan& p, const FlatArgs& fa)
     fs.queue = B.counters.as<unsigned>() + CNT_QUEUE;
     fs.write_cals = 0;
     fs.dbg = nullptr;
+    fs.tail_order = nullptr; // (plan_tail)
+    fs.tail_first = fs.tail_n = 0;
     return fs;
+}
+
+// the table of F5's last hand-outs, built on the job's stream from cal_off (after pool_layout_kernel, before F5) and named in the launch's
+// arguments.  A job that fits the grid makes no draw and gets no launch here; nor does any job with the shift off.  The table's buffer
+// is reserved with the job's others (plan_job): nothing is allocated between the submissions of a sequence.
+void plan_tail(const JobPlan& p, FusedScoreArgs& fs)
+{
+    EnumBuffers& B = p.B;
+    const int W = f5_grid(p.n, fs.f.max_read_len).waves();
+    const int shift = f5_tail_shift(W), T = f5_tail_window(p.n, W, shift); // (T <= min(n, F5_TAIL_MAX): f5_tail_shift)
+    if (T == 0) return;
+    launch_tail_order(p.st, TailArgs{ fs.f.cal_off, p.n - T, T, shift, B.tail_order.as<int32_t>() });
+    ++g_tail_launches;
+    fs.tail_order = B.tail_order.as<int32_t>();
+    fs.tail_first = uint32_t(p.n - T);
+    fs.tail_n = uint32_t(T);
 }
 
 // stage 3's arrays: per candidate alignment (n_cals: the count, or a capacity), per base, a record per read
@@ -2862,8 +3049,9 @@ int run_one_wait(const JobPlan& p, SkEnumOutput* out, bool* redo)
     const FlatArgs fa = flat_args(p, n_cap, true, B.cal_off_z.as<int32_t>(), nullptr, false);
     SK_LAUNCH(pool_bounds_kernel, dim3(e2_blocks), dim3(256), 0, st, fa);
     SK_LAUNCH(pool_layout_kernel, dim3((n + 63) / 64), dim3(64), 0, st, fa);
-    // F5
-    const FusedScoreArgs fs = fused_args(p, fa);
+    // F5, the table of its last hand-outs first
+    FusedScoreArgs fs = fused_args(p, fa);
+    plan_tail(p, fs);
     launch_flatten_score(n, st, fs);
     // S3: a block per read of the job in either launch; the blocks past a list's length leave at once
     // (the largest read of the heavy list is not known here: LDS for the most a block holds)
@@ -3149,7 +3337,8 @@ int run_staged(const JobPlan& p, SkEnumOutput* out)
     const bool fused_enabled = !(std::getenv("SK_A5_FUSED") != nullptr && std::strcmp(std::getenv("SK_A5_FUSED"), "0") == 0);
     bool chain = !(fused_enabled && in->want_scores && n_cals > 0);
     if (!chain) {
-        const FusedScoreArgs fs = fused_args(p, fa);
+        FusedScoreArgs fs = fused_args(p, fa);
+        plan_tail(p, fs); // (the table of F5's last hand-outs)
         launch_flatten_score(n, st, fs);
         SK_HIP(skrt::getLastError());
         p.lap("F5 flatten + score");
@@ -3237,6 +3426,7 @@ static int f5_timing_report(hipStream_t st)
         SK_HIP(hipEventCreate(&a0));
         SK_HIP(hipEventCreate(&a1));
         FusedScoreArgs f2 = g_last.fs;
+        f2.tail_n = 0; // (the table is the whole job's: these launches end before its window)
         launch_flatten_score(grid, st, f2);
         SK_HIP(hipEventRecord(a0, st));
         for (int k = 0; k < 5; ++k) launch_flatten_score(grid, st, f2);
@@ -3253,6 +3443,25 @@ static int f5_timing_report(hipStream_t st)
                      nblk, sum[8] / nblk, ndrawn, sum[8] / std::max(1, ndrawn), sum[0] / nblk, sum[2] / nblk, sum[4] / nblk, sum[7] / nblk, sum[5] / nblk, sum[6] / nblk, sum[3] / nblk / 100.0,
                      sum[6] / std::max(1.0, sum[3]) * 100.0, last - first,
                      sum[6] / double(last - first));
+    // the drain, by the 100 MHz counter (a read's start is its tenth stamp, its duration the fourth): when the last read was handed
+    // out, when the launch's last read ended, and how long a slot stood empty at the end -- over the W reads that started last (the
+    // last read of each of the grid's W waves, or nearly), the mean of (the launch's end - the read's end)
+    std::vector<std::pair<unsigned long long, unsigned long long>> span; // (start, end) of every stamped read
+    for (int r = 0; r < g_last.n; ++r) {
+        const unsigned long long* s = &h[size_t(r) * F5_STAMPS];
+        if (s[6] != 0) span.emplace_back(s[9], s[9] + s[3]);
+    }
+    if (!span.empty()) {
+        std::sort(span.begin(), span.end());
+        const unsigned long long w0 = span.front().first;
+        unsigned long long w1 = 0;
+        for (const auto& x : span) w1 = std::max(w1, x.second);
+        const size_t W = size_t(f5_grid(g_last.n, fs.f.max_read_len).waves()), n_last = std::min(W, span.size());
+        double idle = 0;
+        for (size_t i = span.size() - n_last; i < span.size(); ++i) idle += double(w1 - span[i].second);
+        std::fprintf(stderr, "[f5-timing] drain: tail window %u hand-outs; last read handed out at %.1f us, last read ended at %.1f us; over the %zu reads that started last a slot stood empty for %.1f us on average\n",
+                     fs.tail_n, double(span.back().first - w0) / 100.0, double(w1 - w0) / 100.0, n_last, idle / double(n_last) / 100.0);
+    }
     return 0;
 }
 
