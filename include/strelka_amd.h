@@ -50,6 +50,8 @@ int sk_init(int device);
 /** sk_init, but fails when the host C library is not the one the kernels restate (sk_libm_restated() would be 0): for
  *  callers that must guarantee results bit-identical to the reference (the adapter, smoke(), bench.py). */
 int sk_init_strict(int device);
+/** Frees everything the library holds on the device and in page-locked memory, after the work in flight has ended.  Pileup stream and
+ *  caller handles are the caller's: destroy them first. */
 void sk_shutdown(void);
 const char* sk_last_error(void);
 int sk_version(void);
@@ -108,6 +110,9 @@ int sk_debug_g3_global_pass_count(void);
  *  math library's double routines stand in; sk_libm_restated() then reports 0); on == 0 restores the sk_init outcome.
  *  Lets the test suite measure the documented 1e-5 bar of that path on a box where the exact path is available. */
 int sk_debug_force_device_libm(int on);
+/** Test hook: the bytes of device and of page-locked host memory that the library's grown buffers hold at the moment (the context's
+ *  arena, every module's kept buffers, live pileup streams and callers).  Both are 0 after sk_shutdown.  Either pointer may be NULL. */
+void sk_debug_grown_bytes(int64_t* device_bytes, int64_t* pinned_bytes);
 /** Test hook for the two decline rules of sk_region_alleles[_dev] that no input reaches: no_edge_deletion != 0 drops the required edge
  *  deletion from the detector's alignment scores, so that the aligner's beginPos may exceed 0 (SK_ALLELE_DECLINE_BEGIN_POS);
  *  ids_twice != 0 makes the kernel add a repeated key's haplotype id twice, so that a key both alternates carry adds up to more than 3

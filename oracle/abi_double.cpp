@@ -55,6 +55,11 @@ int sk_init(int) { g_ready = true; return 0; }
 int sk_init_strict(int) { g_ready = true; return 0; }
 int sk_check_device_errors(void) { return 0; }
 int sk_debug_force_device_libm(int) { return 0; }
+void sk_debug_grown_bytes(int64_t* device_bytes, int64_t* pinned_bytes)
+{
+    if (device_bytes) *device_bytes = 0;
+    if (pinned_bytes) *pinned_bytes = 0;
+}
 void sk_shutdown(void) { g_ready = false; }
 const char* sk_last_error(void) { return g_err.c_str(); }
 int sk_version(void) { return SK_VERSION; }

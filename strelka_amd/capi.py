@@ -229,7 +229,7 @@ assert DIGT_CALL_DTYPE.itemsize == 144 and SOMATIC_CALL_DTYPE.itemsize == 272
 
 # every symbol include/strelka_amd.h declares (tests check the library exports all of them)
 EXPORTS = [
-    "sk_device_count", "sk_host_alloc", "sk_host_free", "sk_init", "sk_init_strict", "sk_check_device_errors", "sk_debug_force_device_libm", "sk_debug_set_g3_variant", "sk_debug_g3_global_pass_count", "sk_shutdown", "sk_last_error", "sk_version", "sk_is_initialized", "sk_sync_mode", "sk_libm_restated", "sk_broker_client", "sk_broker_enable", "sk_broker_serve", "sk_broker_selftest", "sk_get_qscore_tables",
+    "sk_device_count", "sk_host_alloc", "sk_host_free", "sk_init", "sk_init_strict", "sk_check_device_errors", "sk_debug_force_device_libm", "sk_debug_grown_bytes", "sk_debug_set_g3_variant", "sk_debug_g3_global_pass_count", "sk_shutdown", "sk_last_error", "sk_version", "sk_is_initialized", "sk_sync_mode", "sk_libm_restated", "sk_broker_client", "sk_broker_enable", "sk_broker_serve", "sk_broker_selftest", "sk_get_qscore_tables",
     "sk_score_alignments", "sk_score_alignments_dev", "sk_align_evmask_words", "sk_align_prepare", "sk_align_colmat_words", "sk_align_prepare_cols",
     "sk_bgzf_scan", "sk_bgzf_inflate", "sk_bgzf_inflate_prefixed", "sk_bgzf_inflate_dev", "sk_bgzf_deflate_bound", "sk_bgzf_deflate", "sk_bgzf_deflate_dev", "sk_bam_header_end", "sk_bam_scan_records", "sk_bam_decode", "sk_bam_decode_kept", "sk_bam_decode_dev", "sk_normalize_alignments", "sk_normalize_alignments_dev",
     "sk_intake_options_default", "sk_read_intake_obs_bound", "sk_read_intake", "sk_read_intake_dev", "sk_read_intake_scratch_bytes",
@@ -275,6 +275,8 @@ def lib():
             pass
         L = C.CDLL(LIB_PATH)
         L.sk_last_error.restype = C.c_char_p
+        L.sk_debug_grown_bytes.argtypes = [c_void_p, c_void_p]
+        L.sk_debug_grown_bytes.restype = None
         L.sk_align_builder_create.restype = c_void_p
         L.sk_align_builder_error.restype = C.c_char_p
         L.sk_align_builder_error.argtypes = [c_void_p]
@@ -437,6 +439,13 @@ def init_strict(device=0):
 
 def shutdown():
     lib().sk_shutdown()
+
+
+def debug_grown_bytes():
+    """(device bytes, page-locked host bytes) the library's grown buffers hold at the moment (sk_debug_grown_bytes); (0, 0) after shutdown()"""
+    dev, pinned = C.c_int64(-1), C.c_int64(-1)
+    lib().sk_debug_grown_bytes(C.byref(dev), C.byref(pinned))
+    return dev.value, pinned.value
 
 
 def germline_options():

@@ -309,30 +309,6 @@ const char* ar_anchor_issue(const int32_t ref_offset, const int32_t ref_len, con
     return nullptr;
 }
 
-struct ArBuffers
-{
-    enum { N = 8 };
-    void* p[N] = {};
-    size_t cap[N] = {};
-    int reserve(const int i, const size_t bytes)
-    {
-        if (bytes <= cap[i]) return 0;
-        if (p[i]) (void)skrt::free_(p[i]);
-        p[i] = nullptr;
-        cap[i] = 0;
-        const size_t want = bytes + bytes / 4 + 4096;
-        SK_HIP(skrt::malloc_(&p[i], want));
-        cap[i] = want;
-        return 0;
-    }
-};
-ArBuffers& ar_bufs()
-{
-    static ArBuffers b;
-    return b;
-}
-enum { AB_REF = 0, AB_ANCHOR, AB_SPAN_POS, AB_SPAN_OUT, AB_SITES, AB_CAND, AB_REGIONS, AB_STATE };
-
 } // namespace
 
 extern "C" {
@@ -390,18 +366,17 @@ int sk_ref_anchors(const char* ref_seq, int32_t ref_offset, int32_t ref_len, int
     SkContext& ctx = sk_ctx();
     SK_HIP(skrt::setDevice(ctx.device));
     hipStream_t st = ctx.stream;
-    ArBuffers& B = ar_bufs();
-    const size_t span_bytes = sizeof(uint32_t) * AR_MAX_UNIT * size_t(n_span_pos);
-    if (B.reserve(AB_REF, size_t(ref_len) + 16) || B.reserve(AB_ANCHOR, size_t(n_pos) + 16) || B.reserve(AB_SPAN_POS, 4 * size_t(n_span_pos) + 16) ||
-        B.reserve(AB_SPAN_OUT, span_bytes + 16))
+    const size_t n_span = size_t(AR_MAX_UNIT) * size_t(n_span_pos);
+    struct { char* ref; uint8_t* anchor; int32_t* span_pos; uint32_t* span_out; } d;
+    int rc = 0;
+    if (sk_carve(d, [&](SkArena& ar) {
+            return decltype(d){ ar.up(ref_seq, size_t(ref_len), 16, st, rc), ar.take<uint8_t>(size_t(n_pos) + 16), ar.up(span_pos, size_t(n_span_pos), 4, st, rc),
+                                ar.take<uint32_t>(n_span + 4) };
+        }) || rc)
         return 1;
-    if (ref_len > 0) SK_HIP(skrt::memcpyAsync(B.p[AB_REF], ref_seq, size_t(ref_len), hipMemcpyHostToDevice, st));
-    if (n_span_pos > 0) SK_HIP(skrt::memcpyAsync(B.p[AB_SPAN_POS], span_pos, 4 * size_t(n_span_pos), hipMemcpyHostToDevice, st));
-    if (sk_ref_anchors_dev(static_cast<char*>(B.p[AB_REF]), ref_offset, ref_len, init_pos, init_span, win_begin, n_pos, static_cast<uint8_t*>(B.p[AB_ANCHOR]), n_span_pos,
-                           static_cast<int32_t*>(B.p[AB_SPAN_POS]), static_cast<uint32_t*>(B.p[AB_SPAN_OUT]), st))
-        return 1;
-    if (n_pos > 0) SK_HIP(skrt::memcpyAsync(is_anchor, B.p[AB_ANCHOR], size_t(n_pos), hipMemcpyDeviceToHost, st));
-    if (n_span_pos > 0) SK_HIP(skrt::memcpyAsync(span_out, B.p[AB_SPAN_OUT], span_bytes, hipMemcpyDeviceToHost, st));
+    if (sk_ref_anchors_dev(d.ref, ref_offset, ref_len, init_pos, init_span, win_begin, n_pos, d.anchor, n_span_pos, d.span_pos, d.span_out, st)) return 1;
+    if (n_pos > 0) SK_HIP(skrt::memcpyAsync(is_anchor, d.anchor, size_t(n_pos), hipMemcpyDeviceToHost, st));
+    if (n_span_pos > 0) SK_HIP(skrt::memcpyAsync(span_out, d.span_out, sizeof(uint32_t) * n_span, hipMemcpyDeviceToHost, st));
     SK_HIP(skrt::streamSynchronize(st));
     return 0;
 }
@@ -442,34 +417,25 @@ int sk_active_regions(int32_t win_begin, int32_t n_pos, const sk_intake_site* si
     SkContext& ctx = sk_ctx();
     SK_HIP(skrt::setDevice(ctx.device));
     hipStream_t st = ctx.stream;
-    ArBuffers& B = ar_bufs();
     const size_t np = size_t(n_pos);
-    // state block: state_in, state_out, n_regions, and this call's own error word (the sticky flag is the _dev entry's)
-    if (B.reserve(AB_SITES, sizeof(sk_intake_site) * np + 16) || B.reserve(AB_CAND, np + 16) || B.reserve(AB_ANCHOR, np + 16) ||
-        B.reserve(AB_REGIONS, sizeof(sk_active_region) * size_t(bound) + 16) || B.reserve(AB_STATE, 256))
+    // (state_in, state_out and n_regions each in a 256-byte piece of their own; the sticky error flag is the _dev entry's)
+    struct { sk_intake_site* sites; uint8_t* cand; uint8_t* anchor; sk_active_region* regions; sk_ar_state* state_in; sk_ar_state* state_out; int32_t* n; } d;
+    int rc = 0;
+    if (sk_carve(d, [&](SkArena& ar) {
+            return decltype(d){ ar.up(sites, np, 2, st, rc), ar.up(is_candidate, np, 16, st, rc), ar.up(is_anchor, np, 16, st, rc),
+                                ar.take<sk_active_region>(size_t(bound) + 2), ar.up(state_in, 1, 0, st, rc), ar.take<sk_ar_state>(1), ar.take<int32_t>(1) };
+        }) || rc)
         return 1;
-    char* state_block = static_cast<char*>(B.p[AB_STATE]);
-    sk_ar_state* d_in = reinterpret_cast<sk_ar_state*>(state_block);
-    sk_ar_state* d_out = reinterpret_cast<sk_ar_state*>(state_block + 64);
-    int32_t* d_n = reinterpret_cast<int32_t*>(state_block + 128);
-    if (n_pos > 0) {
-        SK_HIP(skrt::memcpyAsync(B.p[AB_SITES], sites, sizeof(sk_intake_site) * np, hipMemcpyHostToDevice, st));
-        SK_HIP(skrt::memcpyAsync(B.p[AB_CAND], is_candidate, np, hipMemcpyHostToDevice, st));
-        SK_HIP(skrt::memcpyAsync(B.p[AB_ANCHOR], is_anchor, np, hipMemcpyHostToDevice, st));
-    }
-    SK_HIP(skrt::memcpyAsync(d_in, state_in, sizeof(sk_ar_state), hipMemcpyHostToDevice, st));
-    if (sk_active_regions_dev(win_begin, n_pos, static_cast<sk_intake_site*>(B.p[AB_SITES]), static_cast<uint8_t*>(B.p[AB_CAND]), static_cast<uint8_t*>(B.p[AB_ANCHOR]), d_in,
-                              d_out, static_cast<sk_active_region*>(B.p[AB_REGIONS]), bound, d_n, st))
-        return 1;
+    if (sk_active_regions_dev(win_begin, n_pos, d.sites, d.cand, d.anchor, d.state_in, d.state_out, d.regions, bound, d.n, st)) return 1;
     sk_ar_state out;
     int32_t n = 0;
-    SK_HIP(skrt::memcpyAsync(&out, d_out, sizeof(sk_ar_state), hipMemcpyDeviceToHost, st));
-    SK_HIP(skrt::memcpyAsync(&n, d_n, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    SK_HIP(skrt::memcpyAsync(&out, d.state_out, sizeof(sk_ar_state), hipMemcpyDeviceToHost, st));
+    SK_HIP(skrt::memcpyAsync(&n, d.n, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     SK_HIP(skrt::streamSynchronize(st));
     if (sk_check_device_errors()) return 1; // the assertion failed mid-window: nothing is emitted
     if (n < 0 || n > bound) return sk_fail("sk_active_regions: region count out of range");
     if (n > 0) {
-        SK_HIP(skrt::memcpyAsync(regions, B.p[AB_REGIONS], sizeof(sk_active_region) * size_t(n), hipMemcpyDeviceToHost, st));
+        SK_HIP(skrt::memcpyAsync(regions, d.regions, sizeof(sk_active_region) * size_t(n), hipMemcpyDeviceToHost, st));
         SK_HIP(skrt::streamSynchronize(st));
     }
     *state_out = out;

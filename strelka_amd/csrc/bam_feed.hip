@@ -1262,22 +1262,15 @@ __global__ __launch_bounds__(64) void normalize_kernel(const NormArgs a)
     a.changed[r] = changed ? 1 : 0;
 }
 
+// the host-buffer entry points' device arrays, kept from call to call (a slice after the other reuses them)
 struct FeedBuffers
 {
-    void* p[10] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-    size_t cap[10] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-    int64_t kept_len = -1; // p[8] holds a stream of this many bytes left by sk_bgzf_inflate_prefixed (-1: nothing kept)
-    int reserve(const int i, const size_t bytes)
-    {
-        if (bytes <= cap[i]) return 0;
-        if (p[i]) (void)skrt::free_(p[i]);
-        p[i] = nullptr;
-        cap[i] = 0;
-        const size_t want = bytes + bytes / 4 + 4096;
-        SK_HIP(skrt::malloc_(&p[i], want));
-        cap[i] = want;
-        return 0;
-    }
+    SkDevBuf comp, block_off, out_off, status; // inflate: the compressed blocks, their offsets, the blocks' results
+    SkDevBuf kept;                             // the inflated stream (after the caller's prefix), which sk_bam_decode_kept reads
+    int64_t kept_len = -1;                     // `kept` holds a stream of this many bytes left by sk_bgzf_inflate_prefixed (-1: nothing kept)
+    SkDevBuf stream, rec_off, rec, read_qual;  // decode
+    SkDevBuf read_off, read_code, path_off, path; // decode and normalise
+    SkDevBuf ref, n_seg, pos, changed;         // normalise
 };
 FeedBuffers& feed_bufs()
 {
@@ -1286,6 +1279,15 @@ FeedBuffers& feed_bufs()
 }
 
 } // namespace
+
+void sk_feed_reset()
+{
+    FeedBuffers& B = feed_bufs();
+    for (SkDevBuf* b : { &B.comp, &B.block_off, &B.out_off, &B.status, &B.kept, &B.stream, &B.rec_off, &B.rec, &B.read_qual, &B.read_off, &B.read_code, &B.path_off,
+                         &B.path, &B.ref, &B.n_seg, &B.pos, &B.changed })
+        b->drop();
+    B.kept_len = -1;
+}
 
 extern "C" {
 
@@ -1361,8 +1363,8 @@ int sk_bgzf_inflate_prefixed(const uint8_t* data, const int64_t* block_off, cons
         // a slice that is only the carried record: `out` and the kept stream are the prefix (the header's contract: out receives
         // prefix_len bytes, then the inflated blocks, and sk_bam_decode_kept decodes from the kept stream)
         FeedBuffers& B0 = feed_bufs();
-        if (B0.reserve(8, size_t(prefix_len) + 16)) return 1;
-        SK_HIP(skrt::memcpyAsync(B0.p[8], prefix, size_t(prefix_len), hipMemcpyHostToDevice, st));
+        if (B0.kept.reserve(size_t(prefix_len) + 16)) return 1;
+        SK_HIP(skrt::memcpyAsync(B0.kept.p, prefix, size_t(prefix_len), hipMemcpyHostToDevice, st));
         if (out != prefix) std::memcpy(out, prefix, size_t(prefix_len));
         SK_HIP(skrt::streamSynchronize(st));
         B0.kept_len = prefix_len;
@@ -1371,22 +1373,22 @@ int sk_bgzf_inflate_prefixed(const uint8_t* data, const int64_t* block_off, cons
     const int64_t in_bytes = block_off[n_blocks] - block_off[0], out_bytes = out_off[n_blocks];
     if (in_bytes < 0 || out_bytes < 0 || out_off[0] != 0) return sk_fail("sk_bgzf_inflate: bad offsets");
     FeedBuffers& B = feed_bufs();
-    if (B.reserve(0, size_t(in_bytes) + 16) || B.reserve(1, 8 * size_t(n_blocks + 1)) || B.reserve(2, 8 * size_t(n_blocks + 1)) ||
-        B.reserve(8, size_t(prefix_len) + size_t(out_bytes) + 16) || B.reserve(4, 4 * size_t(n_blocks)))
+    if (B.comp.reserve(size_t(in_bytes) + 16) || B.block_off.reserve(8 * size_t(n_blocks + 1)) || B.out_off.reserve(8 * size_t(n_blocks + 1)) ||
+        B.kept.reserve(size_t(prefix_len) + size_t(out_bytes) + 16) || B.status.reserve(4 * size_t(n_blocks)))
         return 1;
     std::vector<int64_t> rel(size_t(n_blocks) + 1);
     for (int i = 0; i <= n_blocks; ++i) rel[size_t(i)] = block_off[i] - block_off[0];
-    SK_HIP(skrt::memcpyAsync(B.p[0], data + block_off[0], size_t(in_bytes), hipMemcpyHostToDevice, st));
-    SK_HIP(skrt::memcpyAsync(B.p[1], rel.data(), 8 * size_t(n_blocks + 1), hipMemcpyHostToDevice, st));
-    SK_HIP(skrt::memcpyAsync(B.p[2], out_off, 8 * size_t(n_blocks + 1), hipMemcpyHostToDevice, st));
-    if (prefix_len > 0) SK_HIP(skrt::memcpyAsync(B.p[8], prefix, size_t(prefix_len), hipMemcpyHostToDevice, st));
-    if (sk_bgzf_inflate_dev(static_cast<uint8_t*>(B.p[0]), static_cast<int64_t*>(B.p[1]), static_cast<int64_t*>(B.p[2]), n_blocks,
-                            static_cast<uint8_t*>(B.p[8]) + prefix_len, static_cast<int32_t*>(B.p[4]), st))
+    SK_HIP(skrt::memcpyAsync(B.comp.p, data + block_off[0], size_t(in_bytes), hipMemcpyHostToDevice, st));
+    SK_HIP(skrt::memcpyAsync(B.block_off.p, rel.data(), 8 * size_t(n_blocks + 1), hipMemcpyHostToDevice, st));
+    SK_HIP(skrt::memcpyAsync(B.out_off.p, out_off, 8 * size_t(n_blocks + 1), hipMemcpyHostToDevice, st));
+    if (prefix_len > 0) SK_HIP(skrt::memcpyAsync(B.kept.p, prefix, size_t(prefix_len), hipMemcpyHostToDevice, st));
+    if (sk_bgzf_inflate_dev(B.comp.as<uint8_t>(), B.block_off.as<int64_t>(), B.out_off.as<int64_t>(), n_blocks, B.kept.as<uint8_t>() + prefix_len,
+                            B.status.as<int32_t>(), st))
         return 1;
     std::vector<int32_t> status(static_cast<size_t>(n_blocks));
     if (prefix_len > 0 && out != prefix) std::memcpy(out, prefix, size_t(prefix_len));
-    SK_HIP(skrt::memcpyAsync(out + prefix_len, static_cast<uint8_t*>(B.p[8]) + prefix_len, size_t(out_bytes), hipMemcpyDeviceToHost, st));
-    SK_HIP(skrt::memcpyAsync(status.data(), B.p[4], 4 * size_t(n_blocks), hipMemcpyDeviceToHost, st));
+    SK_HIP(skrt::memcpyAsync(out + prefix_len, B.kept.as<uint8_t>() + prefix_len, size_t(out_bytes), hipMemcpyDeviceToHost, st));
+    SK_HIP(skrt::memcpyAsync(status.data(), B.status.p, 4 * size_t(n_blocks), hipMemcpyDeviceToHost, st));
     SK_HIP(skrt::streamSynchronize(st));
     for (int i = 0; i < n_blocks; ++i)
         if (status[size_t(i)] != INF_OK) {
@@ -1458,24 +1460,23 @@ static int bam_decode_host(const uint8_t* stream, int64_t stream_len, const int6
     const int64_t n_bases = read_off[n_records], n_segs = path_off[n_records];
     FeedBuffers& B = feed_bufs();
     if (kept && B.kept_len != stream_len) return sk_fail("sk_bam_decode_kept: no stream of this length was kept by sk_bgzf_inflate_prefixed");
-    if ((!kept && B.reserve(0, size_t(stream_len) + 16)) || B.reserve(1, 8 * size_t(n_records)) || B.reserve(2, 8 * size_t(n_records + 1)) ||
-        B.reserve(5, 8 * size_t(n_records + 1)) || B.reserve(3, sizeof(sk_bam_record) * size_t(n_records)) || B.reserve(4, size_t(n_bases) + 16) ||
-        B.reserve(6, size_t(n_bases) + 16) || B.reserve(7, sizeof(sk_path_seg) * size_t(n_segs) + 16))
+    if ((!kept && B.stream.reserve(size_t(stream_len) + 16)) || B.rec_off.reserve(8 * size_t(n_records)) || B.read_off.reserve(8 * size_t(n_records + 1)) ||
+        B.path_off.reserve(8 * size_t(n_records + 1)) || B.rec.reserve(sizeof(sk_bam_record) * size_t(n_records)) || B.read_code.reserve(size_t(n_bases) + 16) ||
+        B.read_qual.reserve(size_t(n_bases) + 16) || B.path.reserve(sizeof(sk_path_seg) * size_t(n_segs) + 16))
         return 1;
-    if (!kept) SK_HIP(skrt::memcpyAsync(B.p[0], stream, size_t(stream_len), hipMemcpyHostToDevice, st));
-    SK_HIP(skrt::memcpyAsync(B.p[1], rec_off, 8 * size_t(n_records), hipMemcpyHostToDevice, st));
-    SK_HIP(skrt::memcpyAsync(B.p[2], read_off, 8 * size_t(n_records + 1), hipMemcpyHostToDevice, st));
-    SK_HIP(skrt::memcpyAsync(B.p[5], path_off, 8 * size_t(n_records + 1), hipMemcpyHostToDevice, st));
-    if (sk_bam_decode_dev(static_cast<uint8_t*>(kept ? B.p[8] : B.p[0]), static_cast<int64_t*>(B.p[1]), n_records, static_cast<int64_t*>(B.p[2]),
-                          static_cast<int64_t*>(B.p[5]), static_cast<sk_bam_record*>(B.p[3]), static_cast<uint8_t*>(B.p[4]),
-                          static_cast<uint8_t*>(B.p[6]), static_cast<sk_path_seg*>(B.p[7]), st))
+    if (!kept) SK_HIP(skrt::memcpyAsync(B.stream.p, stream, size_t(stream_len), hipMemcpyHostToDevice, st));
+    SK_HIP(skrt::memcpyAsync(B.rec_off.p, rec_off, 8 * size_t(n_records), hipMemcpyHostToDevice, st));
+    SK_HIP(skrt::memcpyAsync(B.read_off.p, read_off, 8 * size_t(n_records + 1), hipMemcpyHostToDevice, st));
+    SK_HIP(skrt::memcpyAsync(B.path_off.p, path_off, 8 * size_t(n_records + 1), hipMemcpyHostToDevice, st));
+    if (sk_bam_decode_dev((kept ? B.kept : B.stream).as<uint8_t>(), B.rec_off.as<int64_t>(), n_records, B.read_off.as<int64_t>(), B.path_off.as<int64_t>(),
+                          B.rec.as<sk_bam_record>(), B.read_code.as<uint8_t>(), B.read_qual.as<uint8_t>(), B.path.as<sk_path_seg>(), st))
         return 1;
-    SK_HIP(skrt::memcpyAsync(rec, B.p[3], sizeof(sk_bam_record) * size_t(n_records), hipMemcpyDeviceToHost, st));
+    SK_HIP(skrt::memcpyAsync(rec, B.rec.p, sizeof(sk_bam_record) * size_t(n_records), hipMemcpyDeviceToHost, st));
     if (n_bases) {
-        SK_HIP(skrt::memcpyAsync(read_code, B.p[4], size_t(n_bases), hipMemcpyDeviceToHost, st));
-        SK_HIP(skrt::memcpyAsync(read_qual, B.p[6], size_t(n_bases), hipMemcpyDeviceToHost, st));
+        SK_HIP(skrt::memcpyAsync(read_code, B.read_code.p, size_t(n_bases), hipMemcpyDeviceToHost, st));
+        SK_HIP(skrt::memcpyAsync(read_qual, B.read_qual.p, size_t(n_bases), hipMemcpyDeviceToHost, st));
     }
-    if (n_segs) SK_HIP(skrt::memcpyAsync(path, B.p[7], sizeof(sk_path_seg) * size_t(n_segs), hipMemcpyDeviceToHost, st));
+    if (n_segs) SK_HIP(skrt::memcpyAsync(path, B.path.p, sizeof(sk_path_seg) * size_t(n_segs), hipMemcpyDeviceToHost, st));
     SK_HIP(skrt::streamSynchronize(st));
     return 0;
 }
@@ -1533,25 +1534,24 @@ int sk_normalize_alignments(const char* ref_seq, int32_t ref_offset, int32_t ref
     hipStream_t st = ctx.stream;
     const int64_t n_bases = read_off[n_reads], n_segs = path_off[n_reads];
     FeedBuffers& B = feed_bufs();
-    if (B.reserve(0, size_t(ref_len) + 16) || B.reserve(1, 8 * size_t(n_reads + 1)) || B.reserve(2, size_t(n_bases) + 16) || B.reserve(3, 8 * size_t(n_reads + 1)) ||
-        B.reserve(4, 4 * size_t(n_reads)) || B.reserve(5, sizeof(sk_path_seg) * size_t(n_segs) + 16) || B.reserve(6, 4 * size_t(n_reads)) ||
-        B.reserve(7, size_t(n_reads) + 16))
+    if (B.ref.reserve(size_t(ref_len) + 16) || B.read_off.reserve(8 * size_t(n_reads + 1)) || B.read_code.reserve(size_t(n_bases) + 16) ||
+        B.path_off.reserve(8 * size_t(n_reads + 1)) || B.n_seg.reserve(4 * size_t(n_reads)) || B.path.reserve(sizeof(sk_path_seg) * size_t(n_segs) + 16) ||
+        B.pos.reserve(4 * size_t(n_reads)) || B.changed.reserve(size_t(n_reads) + 16))
         return 1;
-    SK_HIP(skrt::memcpyAsync(B.p[0], ref_seq, size_t(ref_len), hipMemcpyHostToDevice, st));
-    SK_HIP(skrt::memcpyAsync(B.p[1], read_off, 8 * size_t(n_reads + 1), hipMemcpyHostToDevice, st));
-    if (n_bases) SK_HIP(skrt::memcpyAsync(B.p[2], read_code, size_t(n_bases), hipMemcpyHostToDevice, st));
-    SK_HIP(skrt::memcpyAsync(B.p[3], path_off, 8 * size_t(n_reads + 1), hipMemcpyHostToDevice, st));
-    SK_HIP(skrt::memcpyAsync(B.p[4], n_seg, 4 * size_t(n_reads), hipMemcpyHostToDevice, st));
-    if (n_segs) SK_HIP(skrt::memcpyAsync(B.p[5], path, sizeof(sk_path_seg) * size_t(n_segs), hipMemcpyHostToDevice, st));
-    SK_HIP(skrt::memcpyAsync(B.p[6], pos, 4 * size_t(n_reads), hipMemcpyHostToDevice, st));
-    if (sk_normalize_alignments_dev(static_cast<char*>(B.p[0]), ref_offset, ref_len, n_reads, static_cast<int64_t*>(B.p[1]), static_cast<uint8_t*>(B.p[2]),
-                                    static_cast<int64_t*>(B.p[3]), static_cast<int32_t*>(B.p[4]), static_cast<sk_path_seg*>(B.p[5]),
-                                    static_cast<int32_t*>(B.p[6]), static_cast<uint8_t*>(B.p[7]), st))
+    SK_HIP(skrt::memcpyAsync(B.ref.p, ref_seq, size_t(ref_len), hipMemcpyHostToDevice, st));
+    SK_HIP(skrt::memcpyAsync(B.read_off.p, read_off, 8 * size_t(n_reads + 1), hipMemcpyHostToDevice, st));
+    if (n_bases) SK_HIP(skrt::memcpyAsync(B.read_code.p, read_code, size_t(n_bases), hipMemcpyHostToDevice, st));
+    SK_HIP(skrt::memcpyAsync(B.path_off.p, path_off, 8 * size_t(n_reads + 1), hipMemcpyHostToDevice, st));
+    SK_HIP(skrt::memcpyAsync(B.n_seg.p, n_seg, 4 * size_t(n_reads), hipMemcpyHostToDevice, st));
+    if (n_segs) SK_HIP(skrt::memcpyAsync(B.path.p, path, sizeof(sk_path_seg) * size_t(n_segs), hipMemcpyHostToDevice, st));
+    SK_HIP(skrt::memcpyAsync(B.pos.p, pos, 4 * size_t(n_reads), hipMemcpyHostToDevice, st));
+    if (sk_normalize_alignments_dev(B.ref.as<char>(), ref_offset, ref_len, n_reads, B.read_off.as<int64_t>(), B.read_code.as<uint8_t>(), B.path_off.as<int64_t>(),
+                                    B.n_seg.as<int32_t>(), B.path.as<sk_path_seg>(), B.pos.as<int32_t>(), B.changed.as<uint8_t>(), st))
         return 1;
-    SK_HIP(skrt::memcpyAsync(n_seg, B.p[4], 4 * size_t(n_reads), hipMemcpyDeviceToHost, st));
-    if (n_segs) SK_HIP(skrt::memcpyAsync(path, B.p[5], sizeof(sk_path_seg) * size_t(n_segs), hipMemcpyDeviceToHost, st));
-    SK_HIP(skrt::memcpyAsync(pos, B.p[6], 4 * size_t(n_reads), hipMemcpyDeviceToHost, st));
-    SK_HIP(skrt::memcpyAsync(changed, B.p[7], size_t(n_reads), hipMemcpyDeviceToHost, st));
+    SK_HIP(skrt::memcpyAsync(n_seg, B.n_seg.p, 4 * size_t(n_reads), hipMemcpyDeviceToHost, st));
+    if (n_segs) SK_HIP(skrt::memcpyAsync(path, B.path.p, sizeof(sk_path_seg) * size_t(n_segs), hipMemcpyDeviceToHost, st));
+    SK_HIP(skrt::memcpyAsync(pos, B.pos.p, 4 * size_t(n_reads), hipMemcpyDeviceToHost, st));
+    SK_HIP(skrt::memcpyAsync(changed, B.changed.p, size_t(n_reads), hipMemcpyDeviceToHost, st));
     SK_HIP(skrt::streamSynchronize(st));
     return 0;
 }

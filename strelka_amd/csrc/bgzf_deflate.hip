@@ -701,30 +701,25 @@ __global__ __launch_bounds__(256) void bgzf_pack_kernel(const uint8_t* slots, co
 // device scratch of the deflate entry points (grown on demand, never shrunk; the library's own: one deflate in flight per process)
 struct DeflateBuffers
 {
-    void* p[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-    size_t cap[6] = { 0, 0, 0, 0, 0, 0 };
-    int reserve(const int i, const size_t bytes)
-    {
-        if (bytes <= cap[i]) return 0;
-        if (p[i]) (void)skrt::free_(p[i]);
-        p[i] = nullptr;
-        cap[i] = 0;
-        const size_t want = bytes + bytes / 4 + 4096;
-        SK_HIP(skrt::malloc_(&p[i], want));
-        cap[i] = want;
-        return 0;
-    }
+    SkDevBuf slots, tokens, slot_len;
 };
 DeflateBuffers& deflate_bufs()
 {
     static DeflateBuffers b;
     return b;
 }
-enum { DB_SLOTS = 0, DB_TOKENS = 1, DB_SLOT_LEN = 2, DB_IN = 3, DB_OUT = 4, DB_BLOCK_END = 5 };
 
 int64_t deflate_blocks(const int64_t n_bytes) { return (n_bytes + BD_IN - 1) / BD_IN; }
 
 } // namespace
+
+void sk_deflate_reset()
+{
+    DeflateBuffers& B = deflate_bufs();
+    B.slots.drop();
+    B.tokens.drop();
+    B.slot_len.drop();
+}
 
 extern "C" {
 
@@ -751,16 +746,16 @@ int sk_bgzf_deflate_dev(const uint8_t* dev_data, int64_t n_bytes, int level, int
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     DeflateBuffers& B = deflate_bufs();
     const int32_t per_launch = n_blocks < BD_LAUNCH_BLOCKS ? n_blocks : int32_t(BD_LAUNCH_BLOCKS);
-    if (B.reserve(DB_SLOTS, size_t(n_blocks) * BD_SLOT + 16) || B.reserve(DB_SLOT_LEN, 4 * size_t(n_blocks) + 16) ||
-        (level > 0 && B.reserve(DB_TOKENS, size_t(per_launch) * BD_IN * 4 + 16)))
+    if (B.slots.reserve(size_t(n_blocks) * BD_SLOT + 16) || B.slot_len.reserve(4 * size_t(n_blocks) + 16) ||
+        (level > 0 && B.tokens.reserve(size_t(per_launch) * BD_IN * 4 + 16)))
         return 1;
     DeflateArgs a;
     a.data = dev_data;
     a.n_bytes = n_bytes;
     a.n_blocks = n_blocks;
-    a.slots = static_cast<uint8_t*>(B.p[DB_SLOTS]);
-    a.tokens = static_cast<uint32_t*>(B.p[DB_TOKENS]);
-    a.slot_len = static_cast<int32_t*>(B.p[DB_SLOT_LEN]);
+    a.slots = B.slots.as<uint8_t>();
+    a.tokens = B.tokens.as<uint32_t>();
+    a.slot_len = B.slot_len.as<int32_t>();
     for (int32_t first = 0; first < n_blocks; first += per_launch) {
         a.first_block = first;
         const int32_t count = n_blocks - first < per_launch ? n_blocks - first : per_launch;
@@ -791,23 +786,25 @@ int sk_bgzf_deflate(const uint8_t* data, int64_t n_bytes, int level, int with_eo
     SK_HIP(skrt::setDevice(ctx.device));
     hipStream_t st = ctx.stream;
     const int64_t n_blocks = deflate_blocks(n_bytes);
-    DeflateBuffers& B = deflate_bufs();
-    if (B.reserve(DB_IN, size_t(n_bytes) + 16) || B.reserve(DB_OUT, size_t(bound) + 16) || B.reserve(DB_BLOCK_END, 8 * size_t(n_blocks + 1))) return 1;
-    if (n_bytes > 0) SK_HIP(skrt::memcpyAsync(B.p[DB_IN], data, size_t(n_bytes), hipMemcpyHostToDevice, st));
-    if (sk_bgzf_deflate_dev(static_cast<uint8_t*>(B.p[DB_IN]), n_bytes, level, with_eof, static_cast<uint8_t*>(B.p[DB_OUT]), bound,
-                            static_cast<int64_t*>(B.p[DB_BLOCK_END]), st))
+    // (the arena is this call's until it returns: sk_bgzf_deflate_dev works in the module's own slots, tokens and slot lengths)
+    struct { uint8_t* in; uint8_t* out; int64_t* block_end; } d;
+    int rc = 0;
+    if (sk_carve(d, [&](SkArena& ar) {
+            return decltype(d){ ar.up(data, size_t(n_bytes), 16, st, rc), ar.take<uint8_t>(size_t(bound) + 16), ar.take<int64_t>(size_t(n_blocks + 1)) };
+        }) || rc)
         return 1;
+    if (sk_bgzf_deflate_dev(d.in, n_bytes, level, with_eof, d.out, bound, d.block_end, st)) return 1;
     std::vector<int32_t> slot_len(static_cast<size_t>(n_blocks));
     int64_t total = 0;
-    SK_HIP(skrt::memcpyAsync(&total, static_cast<int64_t*>(B.p[DB_BLOCK_END]) + n_blocks, 8, hipMemcpyDeviceToHost, st));
-    if (n_blocks > 0) SK_HIP(skrt::memcpyAsync(slot_len.data(), B.p[DB_SLOT_LEN], 4 * size_t(n_blocks), hipMemcpyDeviceToHost, st));
+    SK_HIP(skrt::memcpyAsync(&total, d.block_end + n_blocks, 8, hipMemcpyDeviceToHost, st));
+    if (n_blocks > 0) SK_HIP(skrt::memcpyAsync(slot_len.data(), deflate_bufs().slot_len.p, 4 * size_t(n_blocks), hipMemcpyDeviceToHost, st));
     SK_HIP(skrt::streamSynchronize(st));
     for (int64_t i = 0; i < n_blocks; ++i)
         if (slot_len[size_t(i)] <= 0 || slot_len[size_t(i)] > BD_SLOT)
             return sk_fail("sk_bgzf_deflate: block " + std::to_string(i) + ": the emitted size differs from the priced one");
     if (total < 0 || total > bound) return sk_fail("sk_bgzf_deflate: stream size out of range");
     if (total > 0) {
-        SK_HIP(skrt::memcpyAsync(out, B.p[DB_OUT], size_t(total), hipMemcpyDeviceToHost, st));
+        SK_HIP(skrt::memcpyAsync(out, d.out, size_t(total), hipMemcpyDeviceToHost, st));
         SK_HIP(skrt::streamSynchronize(st));
     }
     *out_bytes = total;

@@ -80,27 +80,6 @@ __global__ __launch_bounds__(64) void gvcf_plain_run_kernel(const skgvcf::SitePo
     runs[i] = skgvcf::plain_run(pod, tiles, n, i, frac_tol, abs_tol);
 }
 
-struct GvcfBuffers
-{
-    void* p[3] = { nullptr, nullptr, nullptr };
-    size_t cap[3] = { 0, 0, 0 };
-    int reserve(const int i, const size_t bytes)
-    {
-        if (bytes <= cap[i]) return 0;
-        if (p[i]) (void)skrt::free_(p[i]);
-        p[i] = nullptr;
-        cap[i] = 0;
-        SK_HIP(skrt::malloc_(&p[i], bytes + bytes / 4 + 256));
-        cap[i] = bytes + bytes / 4 + 256;
-        return 0;
-    }
-};
-GvcfBuffers& gvcf_bufs()
-{
-    static GvcfBuffers b;
-    return b;
-}
-
 } // namespace
 
 extern "C" {
@@ -161,21 +140,17 @@ int sk_gvcf_plain_runs(const sk_gvcf_site_summary* summary, const uint32_t* clea
         clean_off[i + 1] = clean_off[i] + clean_count[i];
         raw_off[i + 1] = raw_off[i] + raw_count[i];
     }
-    auto up = [](const size_t b) { return (b + 255) & ~size_t(255); };
     const size_t N = size_t(n);
-    const size_t o_sum = 0, o_off = o_sum + up(sizeof(sk_gvcf_site_summary) * N), o_mq = o_off + up(16 * (N + 1)), o_pod = o_mq + up(4 * N),
-                 o_runs = o_pod + up(17 * N + 512), total = o_runs + up(sizeof(sk_gvcf_run) * N);
-    GvcfBuffers& B = gvcf_bufs();
-    if (B.reserve(0, total)) return 1;
-    char* d = static_cast<char*>(B.p[0]);
-    SK_HIP(skrt::memcpyAsync(d + o_sum, summary, sizeof(sk_gvcf_site_summary) * N, hipMemcpyHostToDevice, st));
-    SK_HIP(skrt::memcpyAsync(d + o_off, off.data(), 16 * (N + 1), hipMemcpyHostToDevice, st));
-    SK_HIP(skrt::memcpyAsync(d + o_mq, mapq_count, 4 * N, hipMemcpyHostToDevice, st));
-    if (sk_gvcf_plain_runs_dev(reinterpret_cast<const sk_gvcf_site_summary*>(d + o_sum), reinterpret_cast<const int64_t*>(d + o_off),
-                               reinterpret_cast<const int64_t*>(d + o_off) + n + 1, reinterpret_cast<const uint32_t*>(d + o_mq), opt, n, d + o_pod,
-                               reinterpret_cast<sk_gvcf_run*>(d + o_runs), st))
+    // (the pod scratch holds the pods and, behind them, the tiles: sk_gvcf_plain_runs_dev)
+    struct { sk_gvcf_site_summary* summary; int64_t* off; uint32_t* mapq_count; char* pod; sk_gvcf_run* runs; } d;
+    int rc = 0;
+    if (sk_carve(d, [&](SkArena& ar) {
+            return decltype(d){ ar.up(summary, N, 0, st, rc), ar.up(off.data(), 2 * (N + 1), 0, st, rc), ar.up(mapq_count, N, 0, st, rc), ar.take<char>(17 * N + 512),
+                                ar.take<sk_gvcf_run>(N) };
+        }) || rc)
         return 1;
-    SK_HIP(skrt::memcpyAsync(runs, d + o_runs, sizeof(sk_gvcf_run) * N, hipMemcpyDeviceToHost, st));
+    if (sk_gvcf_plain_runs_dev(d.summary, d.off, d.off + n + 1, d.mapq_count, opt, n, d.pod, d.runs, st)) return 1;
+    SK_HIP(skrt::memcpyAsync(runs, d.runs, sizeof(sk_gvcf_run) * N, hipMemcpyDeviceToHost, st));
     SK_HIP(skrt::streamSynchronize(st)); // (`off` is pageable: the copies above have finished by now)
     return 0;
 }
@@ -191,26 +166,22 @@ int sk_gvcf_site_summaries(const sk_pileup_batch* hb, const sk_digt_call* genoty
     hipStream_t st = ctx.stream;
     const size_t n = size_t(hb->n_loci);
     const size_t n_calls = size_t(hb->call_off[n]);
-    auto up = [](const size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t o_off = 0, o_calls = o_off + up(8 * (n + 1)), o_ref = o_calls + up(2 * n_calls + 2), o_pl = o_ref + up(n), o_g = o_pl + up(n),
-                 o_out = o_g + up(sizeof(sk_digt_call) * n), total = o_out + up(sizeof(sk_gvcf_site_summary) * n);
-    GvcfBuffers& B = gvcf_bufs();
-    if (B.reserve(0, total)) return 1;
-    char* d = static_cast<char*>(B.p[0]);
-    SK_HIP(skrt::memcpyAsync(d + o_off, hb->call_off, 8 * (n + 1), hipMemcpyHostToDevice, st));
-    if (n_calls) SK_HIP(skrt::memcpyAsync(d + o_calls, hb->calls, 2 * n_calls, hipMemcpyHostToDevice, st));
-    SK_HIP(skrt::memcpyAsync(d + o_ref, hb->ref_base, n, hipMemcpyHostToDevice, st));
-    if (hb->ploidy) SK_HIP(skrt::memcpyAsync(d + o_pl, hb->ploidy, n, hipMemcpyHostToDevice, st));
-    SK_HIP(skrt::memcpyAsync(d + o_g, genotypes, sizeof(sk_digt_call) * n, hipMemcpyHostToDevice, st));
+    struct { int64_t* call_off; uint16_t* calls; uint8_t* ref_base; uint8_t* ploidy; sk_digt_call* genotypes; sk_gvcf_site_summary* out; } d;
+    int rc = 0;
+    if (sk_carve(d, [&](SkArena& ar) {
+            return decltype(d){ ar.up(hb->call_off, n + 1, 0, st, rc), ar.up(hb->calls, n_calls, 1, st, rc), ar.up(hb->ref_base, n, 0, st, rc),
+                                hb->ploidy ? ar.up(hb->ploidy, n, 0, st, rc) : nullptr, ar.up(genotypes, n, 0, st, rc), ar.take<sk_gvcf_site_summary>(n) };
+        }) || rc)
+        return 1;
     sk_pileup_batch db;
     std::memset(&db, 0, sizeof(db));
     db.n_loci = hb->n_loci;
-    db.call_off = reinterpret_cast<const int64_t*>(d + o_off);
-    db.calls = reinterpret_cast<const uint16_t*>(d + o_calls);
-    db.ref_base = reinterpret_cast<const uint8_t*>(d + o_ref);
-    db.ploidy = hb->ploidy ? reinterpret_cast<const uint8_t*>(d + o_pl) : nullptr;
-    if (sk_gvcf_site_summaries_dev(&db, reinterpret_cast<const sk_digt_call*>(d + o_g), reinterpret_cast<sk_gvcf_site_summary*>(d + o_out), st)) return 1;
-    SK_HIP(skrt::memcpyAsync(out, d + o_out, sizeof(sk_gvcf_site_summary) * n, hipMemcpyDeviceToHost, st));
+    db.call_off = d.call_off;
+    db.calls = d.calls;
+    db.ref_base = d.ref_base;
+    db.ploidy = d.ploidy;
+    if (sk_gvcf_site_summaries_dev(&db, d.genotypes, d.out, st)) return 1;
+    SK_HIP(skrt::memcpyAsync(out, d.out, sizeof(sk_gvcf_site_summary) * n, hipMemcpyDeviceToHost, st));
     SK_HIP(skrt::streamSynchronize(st));
     return 0;
 }
@@ -244,15 +215,14 @@ int sk_gvcf_block_sites(const sk_gvcf_site* sites, int32_t n_sites, uint32_t blo
     SkContext& ctx = sk_ctx();
     SK_HIP(skrt::setDevice(ctx.device));
     hipStream_t st = ctx.stream;
-    GvcfBuffers& B = gvcf_bufs();
-    if (B.reserve(0, sizeof(sk_gvcf_site) * size_t(n_sites)) || B.reserve(1, size_t(n_sites)) || B.reserve(2, sizeof(sk_gvcf_block) * size_t(n_sites))) return 1;
-    SK_HIP(skrt::memcpyAsync(B.p[0], sites, sizeof(sk_gvcf_site) * size_t(n_sites), hipMemcpyHostToDevice, st));
-    SK_HIP(skrt::memsetAsync(B.p[2], 0, sizeof(sk_gvcf_block) * size_t(n_sites), st));
-    if (sk_gvcf_block_sites_dev(static_cast<sk_gvcf_site*>(B.p[0]), n_sites, block_percent_tol, block_abs_tol, static_cast<uint8_t*>(B.p[1]),
-                                static_cast<sk_gvcf_block*>(B.p[2]), st))
-        return 1;
-    SK_HIP(skrt::memcpyAsync(kind, B.p[1], size_t(n_sites), hipMemcpyDeviceToHost, st));
-    SK_HIP(skrt::memcpyAsync(blocks, B.p[2], sizeof(sk_gvcf_block) * size_t(n_sites), hipMemcpyDeviceToHost, st));
+    const size_t n = size_t(n_sites);
+    struct { sk_gvcf_site* sites; uint8_t* kind; sk_gvcf_block* blocks; } d;
+    int rc = 0;
+    if (sk_carve(d, [&](SkArena& ar) { return decltype(d){ ar.up(sites, n, 0, st, rc), ar.take<uint8_t>(n), ar.take<sk_gvcf_block>(n) }; }) || rc) return 1;
+    SK_HIP(skrt::memsetAsync(d.blocks, 0, sizeof(sk_gvcf_block) * n, st));
+    if (sk_gvcf_block_sites_dev(d.sites, n_sites, block_percent_tol, block_abs_tol, d.kind, d.blocks, st)) return 1;
+    SK_HIP(skrt::memcpyAsync(kind, d.kind, n, hipMemcpyDeviceToHost, st));
+    SK_HIP(skrt::memcpyAsync(blocks, d.blocks, sizeof(sk_gvcf_block) * n, hipMemcpyDeviceToHost, st));
     SK_HIP(skrt::streamSynchronize(st));
     return 0;
 }

@@ -1282,52 +1282,6 @@ int sk_pileup_reads(const sk_read_batch* hb, const sk_pileup_options* opt, const
 namespace
 {
 
-struct DevBuf
-{
-    void* p = nullptr;
-    size_t cap = 0;
-    int need(const size_t bytes)
-    {
-        if (bytes <= cap) return 0;
-        if (p) (void)skrt::free_(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = bytes + bytes / 2 + 4096;
-        if (skrt::malloc_(&p, want) != hipSuccess) return 1;
-        cap = want;
-        return 0;
-    }
-    void drop()
-    {
-        if (p) (void)skrt::free_(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
-struct PinBuf
-{
-    void* p = nullptr;
-    size_t cap = 0;
-    int need(const size_t bytes)
-    {
-        if (bytes <= cap) return 0;
-        if (p) (void)skrt::hostFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = bytes + bytes / 2 + 4096;
-        if (skrt::hostMalloc(&p, want) != hipSuccess) return 1;
-        cap = want;
-        return 0;
-    }
-    void drop()
-    {
-        if (p) (void)skrt::hostFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
 __global__ void ref_base_id_kernel(const char* ref_seq, const int ref_offset, const int ref_len, const int begin, const int n,
                                    uint8_t* out)
 {
@@ -1403,7 +1357,7 @@ struct sk_pileup_stream
     bool has_region = false;
     int32_t ref_offset = 0, ref_len = 0;
     int32_t region_begin = 0, region_end = 0;
-    DevBuf d_ref, d_mask, d_spandel, d_submapped;
+    SkDevBuf d_ref, d_mask, d_spandel, d_submapped;
     // carried reads: metadata on the host, records and spans on the device
     std::vector<int32_t> c_len, c_nseg, c_pos;
     std::vector<uint8_t> c_mapq, c_level;
@@ -1412,16 +1366,16 @@ struct sk_pileup_stream
     int64_t c_tail_base = 0; // where the carried reads' records start in d_rec[cur]
     int64_t c_tail_read = 0; // ... and their spans in d_span[cur]
     int cur = 0;
-    DevBuf d_rec[2], d_span[2];
+    SkDevBuf d_rec[2], d_span[2];
     bool has_prev = false;
     int32_t next_begin = 0;
-    DevBuf d_in2[2], d_work, d_out; // (two input blocks used alternately: with want_evs the carried reads' bases and qualities are copied across)
+    SkDevBuf d_in2[2], d_work, d_out; // (two input blocks used alternately: with want_evs the carried reads' bases and qualities are copied across)
     int cur_in = 0;
     // the output block of a push: OUT_BLOCKS of them in rotation, so that a window's arrays outlive the next pushes (strelka_amd.h,
     // sk_pileup_window: the caller reads the bulk of a window -- the EVS words -- where the push left it, or not at all)
-    PinBuf h_in, h_out_blocks[SK_PILEUP_WINDOW_LIFETIME + 1];
+    SkPinBuf h_in, h_out_blocks[SK_PILEUP_WINDOW_LIFETIME + 1];
     int out_block = 0;
-    PinBuf& h_out_cur() { return h_out_blocks[out_block]; }
+    SkPinBuf& h_out_cur() { return h_out_blocks[out_block]; }
     int64_t pushes = 0, reads_in = 0;
     // the push in flight (stream_enqueue -> stream_finish)
     InLay li;
@@ -1438,8 +1392,8 @@ struct sk_somatic_pileup_stream
     sk_somatic_snv_options sopt;
     bool genotype = false;
     bool tier2 = false;
-    DevBuf d_call; // forced flags, somatic records, the wrapper's scratch
-    PinBuf h_forced, h_geno;
+    SkDevBuf d_call; // forced flags, somatic records, the wrapper's scratch
+    SkPinBuf h_forced, h_geno;
     bool in_flight = false; // between sk_somatic_pileup_stream_push_begin and _finish
     int p_loci = 0;         // ... the positions of the window in flight
 };
@@ -1562,7 +1516,7 @@ int stream_enqueue(sk_pileup_stream* s, const sk_read_batch* reads, const int32_
     const InLay prev_li = s->li;
     const int prev_in = s->cur_in;
     s->cur_in ^= 1;
-    DevBuf& d_in = s->d_in2[s->cur_in];
+    SkDevBuf& d_in = s->d_in2[s->cur_in];
     InLay& li = s->li;
     {
         int64_t o = 0;
@@ -1580,7 +1534,7 @@ int stream_enqueue(sk_pileup_stream* s, const sk_read_batch* reads, const int32_
         li.total = o;
     }
     const double tq0 = g_push_seconds.on ? PushSeconds::now() : 0.0;
-    if (s->h_in.need(size_t(li.total)) || d_in.need(size_t(li.total))) return sk_fail("sk_pileup_stream_push: out of memory (input block)");
+    if (s->h_in.reserve(size_t(li.total), 2) || d_in.reserve(size_t(li.total), 2)) return sk_fail("sk_pileup_stream_push: out of memory (input block)");
     const double tq1 = g_push_seconds.on ? PushSeconds::now() : 0.0;
     char* hi = static_cast<char*>(s->h_in.p);
     {
@@ -1657,7 +1611,7 @@ int stream_enqueue(sk_pileup_stream* s, const sk_read_batch* reads, const int32_
 
     // ---- records and spans: the carried tail moves to the front of the other buffer
     const int nxt = s->cur ^ 1;
-    if (s->d_rec[nxt].need(size_t(2 * std::max<int64_t>(n_bases, 1))) || s->d_span[nxt].need(size_t(8 * std::max(n, 1))))
+    if (s->d_rec[nxt].reserve(size_t(2 * std::max<int64_t>(n_bases, 1)), 2) || s->d_span[nxt].reserve(size_t(8 * std::max(n, 1)), 2))
         return sk_fail("sk_pileup_stream_push: out of device memory (records)");
     if (s->c_bases > 0) add_copy(static_cast<char*>(s->d_rec[s->cur].p) + 2 * s->c_tail_base, s->d_rec[nxt].p, 2 * s->c_bases);
     if (n_c > 0) add_copy(static_cast<char*>(s->d_span[s->cur].p) + 8 * s->c_tail_read, s->d_span[nxt].p, int64_t(8) * n_c);
@@ -1724,7 +1678,7 @@ int stream_enqueue(sk_pileup_stream* s, const sk_read_batch* reads, const int32_
         ol.total = o;
     }
     s->out_block = (s->out_block + 1) % (SK_PILEUP_WINDOW_LIFETIME + 1);
-    if (s->d_work.need(size_t(wl.total)) || s->d_out.need(size_t(ol.total)) || s->h_out_cur().need(size_t(ol.total)))
+    if (s->d_work.reserve(size_t(wl.total), 2) || s->d_out.reserve(size_t(ol.total), 2) || s->h_out_cur().reserve(size_t(ol.total), 2))
         return sk_fail("sk_pileup_stream_push: out of memory (work / output blocks)");
     char* dw = static_cast<char*>(s->d_work.p);
     char* dout = static_cast<char*>(s->d_out.p);
@@ -1943,7 +1897,7 @@ void stream_drop(sk_pileup_stream* s)
     s->d_rec[0].drop(); s->d_rec[1].drop(); s->d_span[0].drop(); s->d_span[1].drop();
     s->d_in2[0].drop(); s->d_in2[1].drop(); s->d_work.drop(); s->d_out.drop();
     s->h_in.drop();
-    for (PinBuf& b : s->h_out_blocks) b.drop();
+    for (SkPinBuf& b : s->h_out_blocks) b.drop();
 }
 
 } // namespace
@@ -2009,8 +1963,8 @@ int sk_pileup_stream_begin_region(sk_pileup_stream* s, const char* ref_seq, cons
     SK_HIP(skrt::setDevice(ctx.device));
     hipStream_t st = ctx.stream;
     const size_t n_region = size_t(report_end - report_begin);
-    if (s->d_ref.need(size_t(ref_len) + 1) || s->d_mask.need(size_t(ref_len) + 1) || s->d_spandel.need(4 * n_region + 4) ||
-        s->d_submapped.need(4 * n_region + 4))
+    if (s->d_ref.reserve(size_t(ref_len) + 1, 2) || s->d_mask.reserve(size_t(ref_len) + 1, 2) || s->d_spandel.reserve(4 * n_region + 4, 2) ||
+        s->d_submapped.reserve(4 * n_region + 4, 2))
         return sk_fail("sk_pileup_stream_begin_region: out of device memory");
     if (ref_len > 0) SK_HIP(skrt::memcpyAsync(s->d_ref.p, ref_seq, size_t(ref_len), hipMemcpyHostToDevice, st));
     SK_HIP(skrt::memsetAsync(s->d_mask.p, 0, size_t(ref_len) + 1, st));
@@ -2212,8 +2166,8 @@ int sk_somatic_pileup_stream_push_begin(sk_somatic_pileup_stream* p, const sk_re
     if (p->genotype && n_loci > 0) {
         const size_t forced_bytes = size_t(align256(n_loci));
         const size_t scratch_bytes = sk_somatic_snv_tiers_scratch_bytes(n_loci);
-        if (p->d_call.need(forced_bytes + size_t(align256(int64_t(geno_bytes))) + scratch_bytes) || p->h_forced.need(forced_bytes) ||
-            p->h_geno.need(geno_bytes))
+        if (p->d_call.reserve(forced_bytes + size_t(align256(int64_t(geno_bytes))) + scratch_bytes, 2) || p->h_forced.reserve(forced_bytes, 2) ||
+            p->h_geno.reserve(geno_bytes, 2))
             return sk_fail("sk_somatic_pileup_stream_push: out of memory (somatic records)");
         uint8_t* hf = static_cast<uint8_t*>(p->h_forced.p);
         for (int i = 0; i < n_loci; ++i) {

@@ -57,6 +57,8 @@ extern "C" int sk_enum_device_run(const SkEnumInput* in, SkEnumOutput* out);
 /** candidate alignments [first, first + count) of run `generation`, from the device's buffers; 1 when another run has replaced them */
 extern "C" int sk_enum_device_fetch_cals(uint64_t generation, int32_t first, int32_t count, skcore::PCal* out);
 
+/** the generation of the process's last run (0: none yet); tests keep it across sk_shutdown */
+extern "C" uint64_t sk_enum_device_generation(void);
 /** scores [first, first + count) of run `generation`; 1 when another run has replaced them */
 extern "C" int sk_enum_device_fetch_scores(uint64_t generation, int32_t first, int32_t count, double* out);
 /** jobs of this process: run as one fixed sequence with one wait, of those run again the staged way, run the staged way from the start */

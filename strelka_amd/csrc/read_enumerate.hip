@@ -2309,27 +2309,6 @@ __global__ __launch_bounds__(64 * WAVES) void stage3_kernel(const Stage3Args a)
 // ---------------------------------------------------------------------------------------------------------------------
 // buffers: grown on demand, kept for the life of the process (one job after the other reuses them)
 
-template <bool PINNED>
-struct Buf
-{
-    void* p = nullptr;
-    size_t cap = 0;
-    int reserve(const size_t bytes)
-    {
-        if (bytes <= cap) return 0;
-        if (p) (void)(PINNED ? skrt::hostFree(p) : skrt::free_(p));
-        p = nullptr;
-        cap = 0;
-        const size_t want = bytes + bytes / 4 + 4096;
-        SK_HIP(PINNED ? skrt::hostMalloc(&p, want) : skrt::malloc_(&p, want));
-        cap = want;
-        return 0;
-    }
-    template <typename T> T* as() const { return static_cast<T*>(p); }
-};
-using DevBuf = Buf<false>;
-using HostBuf = Buf<true>; // pinned
-
 struct View // a piece of one of the arenas below
 {
     void* p = nullptr;
@@ -2341,21 +2320,33 @@ struct View // a piece of one of the arenas below
 // array that starts at zero in `zero_arena` (one fill; the parts the host reads come back in one copy per synchronisation point)
 struct EnumBuffers
 {
-    DevBuf in_arena, zero_arena, minmax_arena, mask_arena;
-    HostBuf h_in_arena, h_zero_arena;
+    SkDevBuf in_arena, zero_arena, minmax_arena, mask_arena;
+    SkPinBuf h_in_arena, h_zero_arena;
     View tab, ins, toggle, ref, ref_code, ins_code, reads, read_off, read_code, read_qual, r2i, i2r, orig, map_level;
     View counters, status, warn, n_raw, hap_len, fill, n_uniq, consulted;
     View win_begin, ins_lo, win_end, ins_hi, evmask, addmask;
     View h_counters, h_status, h_warn, h_n_raw, h_hap_len, h_n_uniq, h_consulted;
     View cal_off_z, h_cal_off_z;
-    DevBuf level_a, level_b, pool, leaf_read, leaf_hash;
-    DevBuf raw_off, grouped, ghash, gkey, dup, sorted;
-    DevBuf n_ops, win_len, n_ins, ins_idx, ins_off, n_seg8;
-    DevBuf cal_off, hap_off, cals, hap_code, op_off, ops, entries, scores, colmat, colmat_off;
-    DevBuf s3_order, s3_smooth, s3_flag, s3_rm_type, s3_rm_pos, s3_key, s3_sorted_score, s3_sorted_hash, s3_next_same, s3_range_end, s3_removed, s3_out, s3_list;
-    DevBuf tail_order; // F5's last hand-outs (tail_order_kernel)
-    HostBuf h_s3_out, h_s3_list;
-    HostBuf h_raw_off, h_n_ops, h_cal_off, h_hap_off, h_op_off, h_cals, h_scores, h_colmat_off;
+    SkDevBuf level_a, level_b, pool, leaf_read, leaf_hash;
+    SkDevBuf raw_off, grouped, ghash, gkey, dup, sorted;
+    SkDevBuf n_ops, win_len, n_ins, ins_idx, ins_off, n_seg8;
+    SkDevBuf cal_off, hap_off, cals, hap_code, op_off, ops, entries, scores, colmat, colmat_off;
+    SkDevBuf s3_order, s3_smooth, s3_flag, s3_rm_type, s3_rm_pos, s3_key, s3_sorted_score, s3_sorted_hash, s3_next_same, s3_range_end, s3_removed, s3_out, s3_list;
+    SkDevBuf tail_order; // F5's last hand-outs (tail_order_kernel)
+    SkPinBuf h_s3_out, h_s3_list;
+    SkPinBuf h_raw_off, h_n_ops, h_cal_off, h_hap_off, h_op_off, h_cals, h_scores, h_colmat_off;
+    void drop() // every block above, then the views into them
+    {
+        for (SkDevBuf* b : { &in_arena, &zero_arena, &minmax_arena, &mask_arena, &level_a, &level_b, &pool, &leaf_read, &leaf_hash, &raw_off, &grouped, &ghash,
+                             &gkey, &dup, &sorted, &n_ops, &win_len, &n_ins, &ins_idx, &ins_off, &n_seg8, &cal_off, &hap_off, &cals, &hap_code, &op_off, &ops,
+                             &entries, &scores, &colmat, &colmat_off, &s3_order, &s3_smooth, &s3_flag, &s3_rm_type, &s3_rm_pos, &s3_key, &s3_sorted_score,
+                             &s3_sorted_hash, &s3_next_same, &s3_range_end, &s3_removed, &s3_out, &s3_list, &tail_order })
+            b->drop();
+        for (SkPinBuf* b : { &h_in_arena, &h_zero_arena, &h_s3_out, &h_s3_list, &h_raw_off, &h_n_ops, &h_cal_off, &h_hap_off, &h_op_off, &h_cals, &h_scores,
+                             &h_colmat_off })
+            b->drop();
+        *this = EnumBuffers();
+    }
 };
 EnumBuffers& bufs()
 {
@@ -2365,25 +2356,25 @@ EnumBuffers& bufs()
 
 // a job's reservations, as tables: a device buffer holds at least 256 bytes (an empty array still has an address), a pinned one 64 bytes
 // more than asked for (job_stage_out_kernel writes whole 16-byte words)
-int reserve_dev(std::initializer_list<std::pair<DevBuf&, size_t>> wants) // { buffer, bytes }, ...
+int reserve_dev(std::initializer_list<std::pair<SkDevBuf&, size_t>> wants) // { buffer, bytes }, ...
 {
     for (const auto& w : wants)
         if (w.first.reserve(std::max<size_t>(w.second, 256))) return 1;
     return 0;
 }
-int reserve_pinned(std::initializer_list<std::pair<HostBuf&, size_t>> wants)
+int reserve_pinned(std::initializer_list<std::pair<SkPinBuf&, size_t>> wants)
 {
     for (const auto& w : wants)
         if (w.first.reserve(w.second + 64)) return 1;
     return 0;
 }
 // copies on the job's stream; nothing is submitted for zero bytes
-int copy_up(hipStream_t st, const DevBuf& dst, const void* src, const size_t bytes)
+int copy_up(hipStream_t st, const SkDevBuf& dst, const void* src, const size_t bytes)
 {
     if (bytes > 0) SK_HIP(skrt::memcpyAsync(dst.p, src, bytes, hipMemcpyHostToDevice, st));
     return 0;
 }
-int copy_down(hipStream_t st, const HostBuf& dst, const DevBuf& src, const size_t bytes)
+int copy_down(hipStream_t st, const SkPinBuf& dst, const SkDevBuf& src, const size_t bytes)
 {
     if (bytes > 0) SK_HIP(skrt::memcpyAsync(dst.p, src.p, bytes, hipMemcpyDeviceToHost, st));
     return 0;
@@ -2416,6 +2407,20 @@ struct LastFlat
     double* scores = nullptr;
 } g_last;
 } // namespace
+
+// (the generation counter stays: a caller that kept a generation from before sk_shutdown is refused, not served from another run's memory)
+void sk_enum_reset()
+{
+    bufs().drop();
+    g_n_cals = 0;
+    g_scores = nullptr;
+    g_cals_pool = nullptr;
+    g_cals_list = nullptr;
+    g_cals_gathered = false;
+    g_last.valid = false;
+}
+
+extern "C" uint64_t sk_enum_device_generation(void) { return g_generation; }
 
 extern "C" int sk_enum_device_fetch_scores(const uint64_t generation, const int32_t first, const int32_t count, double* dst)
 {
@@ -3395,15 +3400,16 @@ static int f5_timing_report(hipStream_t st)
 {
     FusedScoreArgs fs = g_last.fs;
     const size_t nb = size_t(g_last.n) * F5_STAMPS;
-    unsigned long long* d = nullptr;
-    SK_HIP(skrt::malloc_(reinterpret_cast<void**>(&d), nb * 8));
+    SkDevBuf dbg; // (this report's own: dropped below)
+    if (dbg.reserve(nb * 8)) return 1;
+    unsigned long long* d = dbg.as<unsigned long long>();
     SK_HIP(skrt::memsetAsync(d, 0, nb * 8, st));
     fs.dbg = d;
     launch_flatten_score(g_last.n, st, fs);
     std::vector<unsigned long long> h(nb);
     SK_HIP(skrt::memcpyAsync(h.data(), d, nb * 8, hipMemcpyDeviceToHost, st));
     SK_HIP(skrt::streamSynchronize(st));
-    (void)skrt::free_(d);
+    dbg.drop();
     double sum[F5_STAMPS] = { 0 };
     unsigned long long first = ~0ull, last = 0;
     int nblk = 0, ndrawn = 0;

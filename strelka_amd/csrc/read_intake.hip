@@ -584,30 +584,6 @@ const char* intake_path_issue(const sk_path_seg* p, const int n, const int64_t r
     return nullptr;
 }
 
-struct IntakeBuffers
-{
-    enum { N = 14 };
-    void* p[N] = {};
-    size_t cap[N] = {};
-    int reserve(const int i, const size_t bytes)
-    {
-        if (bytes <= cap[i]) return 0;
-        if (p[i]) (void)skrt::free_(p[i]);
-        p[i] = nullptr;
-        cap[i] = 0;
-        const size_t want = bytes + bytes / 4 + 4096;
-        SK_HIP(skrt::malloc_(&p[i], want));
-        cap[i] = want;
-        return 0;
-    }
-};
-IntakeBuffers& intake_bufs()
-{
-    static IntakeBuffers b;
-    return b;
-}
-enum { IB_REF = 0, IB_READ_OFF, IB_CODE, IB_PATH_OFF, IB_NSEG, IB_PATH, IB_POS, IB_LOW, IB_READS, IB_OBS_OFF, IB_OBS, IB_SITES, IB_CAND, IB_SCRATCH };
-
 } // namespace
 
 const char* sk_intake_path_issue(const sk_path_seg* path, const int n_seg, const int64_t read_len) { return intake_path_issue(path, n_seg, read_len); }
@@ -722,42 +698,36 @@ int sk_read_intake(const char* ref_seq, int32_t ref_offset, int32_t ref_len, int
     SkContext& ctx = sk_ctx();
     SK_HIP(skrt::setDevice(ctx.device));
     hipStream_t st = ctx.stream;
-    IntakeBuffers& B = intake_bufs();
-    const size_t nr = size_t(n_reads);
+    const size_t nr = size_t(n_reads), no = n_reads > 0 ? nr + 1 : 0; // (nothing of the reads' arrays goes up without reads)
     const size_t scratch_bytes = sk_read_intake_scratch_bytes(n_reads, n_segs, n_pos);
-    if (B.reserve(IB_REF, size_t(ref_len) + 16) || B.reserve(IB_READ_OFF, 8 * (nr + 1)) || B.reserve(IB_CODE, size_t(n_bases) + 16) ||
-        B.reserve(IB_PATH_OFF, 8 * (nr + 1)) || B.reserve(IB_NSEG, 4 * nr + 16) || B.reserve(IB_PATH, sizeof(sk_path_seg) * size_t(n_segs) + 16) ||
-        B.reserve(IB_POS, 4 * nr + 16) || B.reserve(IB_LOW, nr + 16) || B.reserve(IB_READS, sizeof(sk_intake_read) * nr + 16) ||
-        B.reserve(IB_OBS_OFF, 8 * (nr + 1)) || B.reserve(IB_OBS, sizeof(sk_intake_obs) * size_t(bound) + 16) ||
-        B.reserve(IB_SITES, sizeof(sk_intake_site) * size_t(n_pos) + 16) || B.reserve(IB_CAND, size_t(n_pos) + 16) || B.reserve(IB_SCRATCH, scratch_bytes + 16))
+    struct
+    {
+        char* ref; int64_t* read_off; uint8_t* code; int64_t* path_off; int32_t* n_seg; sk_path_seg* path; int32_t* pos; uint8_t* low;
+        sk_intake_read* reads; int64_t* obs_off; sk_intake_obs* obs; sk_intake_site* sites; uint8_t* cand; char* scratch;
+    } d;
+    int rc = 0;
+    // (+ 16 bytes and the like: kernels read whole words past an array's end; sk_read_intake_dev reserves nothing of the arena)
+    if (sk_carve(d, [&](SkArena& ar) {
+            return decltype(d){ ar.up(ref_seq, size_t(ref_len), 16, st, rc), ar.up(read_off, no, 1, st, rc), ar.up(read_code, size_t(n_bases), 16, st, rc),
+                                ar.up(path_off, no, 1, st, rc), ar.up(n_seg, nr, 4, st, rc), ar.up(path, size_t(n_segs), 2, st, rc), ar.up(pos, nr, 4, st, rc),
+                                ar.up(low_mapq, nr, 16, st, rc), ar.take<sk_intake_read>(nr + 1), ar.take<int64_t>(nr + 1), ar.take<sk_intake_obs>(size_t(bound) + 1),
+                                ar.take<sk_intake_site>(size_t(n_pos) + 2), ar.take<uint8_t>(size_t(n_pos) + 16), ar.take<char>(scratch_bytes + 16) };
+        }) || rc)
         return 1;
-    if (ref_len > 0) SK_HIP(skrt::memcpyAsync(B.p[IB_REF], ref_seq, size_t(ref_len), hipMemcpyHostToDevice, st));
-    if (n_reads > 0) {
-        SK_HIP(skrt::memcpyAsync(B.p[IB_READ_OFF], read_off, 8 * (nr + 1), hipMemcpyHostToDevice, st));
-        if (n_bases) SK_HIP(skrt::memcpyAsync(B.p[IB_CODE], read_code, size_t(n_bases), hipMemcpyHostToDevice, st));
-        SK_HIP(skrt::memcpyAsync(B.p[IB_PATH_OFF], path_off, 8 * (nr + 1), hipMemcpyHostToDevice, st));
-        SK_HIP(skrt::memcpyAsync(B.p[IB_NSEG], n_seg, 4 * nr, hipMemcpyHostToDevice, st));
-        if (n_segs) SK_HIP(skrt::memcpyAsync(B.p[IB_PATH], path, sizeof(sk_path_seg) * size_t(n_segs), hipMemcpyHostToDevice, st));
-        SK_HIP(skrt::memcpyAsync(B.p[IB_POS], pos, 4 * nr, hipMemcpyHostToDevice, st));
-        SK_HIP(skrt::memcpyAsync(B.p[IB_LOW], low_mapq, nr, hipMemcpyHostToDevice, st));
-    }
-    if (sk_read_intake_dev(static_cast<char*>(B.p[IB_REF]), ref_offset, ref_len, n_reads, static_cast<int64_t*>(B.p[IB_READ_OFF]),
-                           static_cast<uint8_t*>(B.p[IB_CODE]), static_cast<int64_t*>(B.p[IB_PATH_OFF]), static_cast<int32_t*>(B.p[IB_NSEG]),
-                           static_cast<sk_path_seg*>(B.p[IB_PATH]), static_cast<int32_t*>(B.p[IB_POS]), static_cast<uint8_t*>(B.p[IB_LOW]), opt, win_begin,
-                           n_pos, static_cast<sk_intake_read*>(B.p[IB_READS]), static_cast<int64_t*>(B.p[IB_OBS_OFF]), static_cast<sk_intake_obs*>(B.p[IB_OBS]),
-                           bound, static_cast<sk_intake_site*>(B.p[IB_SITES]), static_cast<uint8_t*>(B.p[IB_CAND]), B.p[IB_SCRATCH], scratch_bytes, st))
+    if (sk_read_intake_dev(d.ref, ref_offset, ref_len, n_reads, d.read_off, d.code, d.path_off, d.n_seg, d.path, d.pos, d.low, opt, win_begin, n_pos, d.reads,
+                           d.obs_off, d.obs, bound, d.sites, d.cand, d.scratch, scratch_bytes, st))
         return 1;
-    if (n_reads > 0) SK_HIP(skrt::memcpyAsync(reads, B.p[IB_READS], sizeof(sk_intake_read) * nr, hipMemcpyDeviceToHost, st));
-    SK_HIP(skrt::memcpyAsync(obs_off, B.p[IB_OBS_OFF], 8 * (nr + 1), hipMemcpyDeviceToHost, st));
+    if (n_reads > 0) SK_HIP(skrt::memcpyAsync(reads, d.reads, sizeof(sk_intake_read) * nr, hipMemcpyDeviceToHost, st));
+    SK_HIP(skrt::memcpyAsync(obs_off, d.obs_off, 8 * (nr + 1), hipMemcpyDeviceToHost, st));
     if (n_pos > 0) {
-        SK_HIP(skrt::memcpyAsync(sites, B.p[IB_SITES], sizeof(sk_intake_site) * size_t(n_pos), hipMemcpyDeviceToHost, st));
-        SK_HIP(skrt::memcpyAsync(is_candidate, B.p[IB_CAND], size_t(n_pos), hipMemcpyDeviceToHost, st));
+        SK_HIP(skrt::memcpyAsync(sites, d.sites, sizeof(sk_intake_site) * size_t(n_pos), hipMemcpyDeviceToHost, st));
+        SK_HIP(skrt::memcpyAsync(is_candidate, d.cand, size_t(n_pos), hipMemcpyDeviceToHost, st));
     }
     SK_HIP(skrt::streamSynchronize(st));
     const int64_t total = obs_off[n_reads];
     if (total < 0 || total > bound) return sk_fail("sk_read_intake: observation count out of range");
     if (total > 0) {
-        SK_HIP(skrt::memcpyAsync(obs, B.p[IB_OBS], sizeof(sk_intake_obs) * size_t(total), hipMemcpyDeviceToHost, st));
+        SK_HIP(skrt::memcpyAsync(obs, d.obs, sizeof(sk_intake_obs) * size_t(total), hipMemcpyDeviceToHost, st));
         SK_HIP(skrt::streamSynchronize(st));
     }
     return 0;

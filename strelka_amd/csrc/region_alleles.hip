@@ -579,30 +579,6 @@ ScratchLayout alleles_scratch_layout(const int64_t region_cap, const int32_t max
     return s;
 }
 
-struct AlleleBuffers
-{
-    enum { N = 10 };
-    void* p[N] = {};
-    size_t cap[N] = {};
-    int reserve(const int i, const size_t bytes)
-    {
-        if (bytes <= cap[i]) return 0;
-        if (p[i]) (void)skrt::free_(p[i]);
-        p[i] = nullptr;
-        cap[i] = 0;
-        const size_t want = bytes + bytes / 4 + 4096;
-        SK_HIP(skrt::malloc_(&p[i], want));
-        cap[i] = want;
-        return 0;
-    }
-};
-AlleleBuffers& allele_bufs()
-{
-    static AlleleBuffers b;
-    return b;
-}
-enum { AB_REF = 0, AB_REGIONS, AB_STATE, AB_HAP, AB_SEQ, AB_RECS, AB_ALLELES, AB_INS, AB_SCRATCH };
-
 // sk_debug_region_alleles: the two decline rules that no input reaches with the detector's scores
 int g_debug_no_edge_deletion = 0, g_debug_ids_twice = 0;
 
@@ -746,39 +722,36 @@ int sk_region_alleles(const char* ref_seq, int32_t ref_offset, int32_t ref_len, 
     SkContext& ctx = sk_ctx();
     SK_HIP(skrt::setDevice(ctx.device));
     hipStream_t st = ctx.stream;
-    AlleleBuffers& B = allele_bufs();
     const size_t ng = size_t(n_regions);
     const size_t scratch_bytes = sk_region_alleles_scratch_bytes(n_regions, max_hap_len);
-    if (B.reserve(AB_REF, size_t(ref_len) + 16) || B.reserve(AB_REGIONS, sizeof(sk_active_region) * ng + 16) || B.reserve(AB_STATE, 256) ||
-        B.reserve(AB_HAP, sizeof(sk_region_haplotypes_rec) * ng + 16) || B.reserve(AB_SEQ, size_t(seq_len) + 16) || B.reserve(AB_RECS, sizeof(sk_region_alleles_rec) * ng + 16) ||
-        B.reserve(AB_ALLELES, sizeof(sk_region_allele) * size_t(allele_bound) + 16) || B.reserve(AB_INS, size_t(insert_bound) + 16) || B.reserve(AB_SCRATCH, scratch_bytes + 16))
+    struct
+    {
+        char* ref; sk_active_region* regions; sk_region_haplotypes_rec* hap; uint8_t* seq; int32_t* n_regions; sk_region_alleles_rec* recs;
+        sk_region_allele* alleles; uint8_t* ins; char* scratch; int64_t* totals; int32_t* prev_end;
+    } d;
+    int rc = 0;
+    // (+ 16 bytes and the like: kernels read whole words past an array's end; a piece starts at a multiple of 256 bytes, as the scratch's
+    // layout wants its base; sk_region_alleles_dev, sk_ga_launch_counted under it and sk_check_device_errors reserve nothing of the arena)
+    if (sk_carve(d, [&](SkArena& ar) {
+            return decltype(d){ ar.up(ref_seq, size_t(ref_len), 16, st, rc), ar.up(regions, ng, 2, st, rc), ar.up(hap_recs, ng, 1, st, rc),
+                                ar.up(seq_pool, size_t(seq_len), 16, st, rc), ar.up(&n_regions, 1, 0, st, rc), ar.take<sk_region_alleles_rec>(ng + 1),
+                                ar.take<sk_region_allele>(size_t(allele_bound) + 1), ar.take<uint8_t>(size_t(insert_bound) + 16), ar.take<char>(scratch_bytes + 16),
+                                ar.take<int64_t>(2), ar.take<int32_t>(1) };
+        }) || rc)
         return 1;
-    if (ref_len > 0) SK_HIP(skrt::memcpyAsync(B.p[AB_REF], ref_seq, size_t(ref_len), hipMemcpyHostToDevice, st));
-    if (n_regions > 0) {
-        SK_HIP(skrt::memcpyAsync(B.p[AB_REGIONS], regions, sizeof(sk_active_region) * ng, hipMemcpyHostToDevice, st));
-        SK_HIP(skrt::memcpyAsync(B.p[AB_HAP], hap_recs, sizeof(sk_region_haplotypes_rec) * ng, hipMemcpyHostToDevice, st));
-    }
-    if (seq_len > 0) SK_HIP(skrt::memcpyAsync(B.p[AB_SEQ], seq_pool, size_t(seq_len), hipMemcpyHostToDevice, st));
-    char* state_block = static_cast<char*>(B.p[AB_STATE]); // n_regions, prev_end_out, then the totals
-    int32_t* d_n = reinterpret_cast<int32_t*>(state_block);
-    int32_t* d_prev = reinterpret_cast<int32_t*>(state_block + 32);
-    int64_t* d_totals = reinterpret_cast<int64_t*>(state_block + 64);
-    SK_HIP(skrt::memcpyAsync(d_n, &n_regions, sizeof(int32_t), hipMemcpyHostToDevice, st));
-    if (sk_region_alleles_dev(static_cast<char*>(B.p[AB_REF]), ref_offset, ref_len, static_cast<sk_active_region*>(B.p[AB_REGIONS]), d_n, n_regions,
-                              static_cast<sk_region_haplotypes_rec*>(B.p[AB_HAP]), static_cast<uint8_t*>(B.p[AB_SEQ]), seq_len, max_indel_size, max_hap_len, prev_end_in,
-                              static_cast<sk_region_alleles_rec*>(B.p[AB_RECS]), static_cast<sk_region_allele*>(B.p[AB_ALLELES]), allele_bound,
-                              static_cast<uint8_t*>(B.p[AB_INS]), insert_bound, d_totals, d_prev, B.p[AB_SCRATCH], scratch_bytes + 16, st))
+    if (sk_region_alleles_dev(d.ref, ref_offset, ref_len, d.regions, d.n_regions, n_regions, d.hap, d.seq, seq_len, max_indel_size, max_hap_len, prev_end_in, d.recs,
+                              d.alleles, allele_bound, d.ins, insert_bound, d.totals, d.prev_end, d.scratch, scratch_bytes + 16, st))
         return 1;
     int64_t t[2] = { 0, 0 };
     int32_t prev = 0;
-    SK_HIP(skrt::memcpyAsync(t, d_totals, sizeof(t), hipMemcpyDeviceToHost, st));
-    SK_HIP(skrt::memcpyAsync(&prev, d_prev, sizeof(prev), hipMemcpyDeviceToHost, st));
-    if (n_regions > 0) SK_HIP(skrt::memcpyAsync(recs, B.p[AB_RECS], sizeof(sk_region_alleles_rec) * ng, hipMemcpyDeviceToHost, st));
+    SK_HIP(skrt::memcpyAsync(t, d.totals, sizeof(t), hipMemcpyDeviceToHost, st));
+    SK_HIP(skrt::memcpyAsync(&prev, d.prev_end, sizeof(prev), hipMemcpyDeviceToHost, st));
+    if (n_regions > 0) SK_HIP(skrt::memcpyAsync(recs, d.recs, sizeof(sk_region_alleles_rec) * ng, hipMemcpyDeviceToHost, st));
     SK_HIP(skrt::streamSynchronize(st));
     if (sk_check_device_errors()) return 1;
     if (t[0] < 0 || t[0] > allele_bound || t[1] < 0 || t[1] > insert_bound) return sk_fail("sk_region_alleles: totals out of range");
-    if (t[0] > 0) SK_HIP(skrt::memcpyAsync(alleles, B.p[AB_ALLELES], sizeof(sk_region_allele) * size_t(t[0]), hipMemcpyDeviceToHost, st));
-    if (t[1] > 0) SK_HIP(skrt::memcpyAsync(insert_pool, B.p[AB_INS], size_t(t[1]), hipMemcpyDeviceToHost, st));
+    if (t[0] > 0) SK_HIP(skrt::memcpyAsync(alleles, d.alleles, sizeof(sk_region_allele) * size_t(t[0]), hipMemcpyDeviceToHost, st));
+    if (t[1] > 0) SK_HIP(skrt::memcpyAsync(insert_pool, d.ins, size_t(t[1]), hipMemcpyDeviceToHost, st));
     SK_HIP(skrt::streamSynchronize(st));
     totals[0] = t[0];
     totals[1] = t[1];

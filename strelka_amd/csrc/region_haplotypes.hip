@@ -742,31 +742,6 @@ u64 hap_hash_mask()
     return ~0ull;
 }
 
-struct HapBuffers
-{
-    enum { N = 20 };
-    void* p[N] = {};
-    size_t cap[N] = {};
-    int reserve(const int i, const size_t bytes)
-    {
-        if (bytes <= cap[i]) return 0;
-        if (p[i]) (void)skrt::free_(p[i]);
-        p[i] = nullptr;
-        cap[i] = 0;
-        const size_t want = bytes + bytes / 4 + 4096;
-        SK_HIP(skrt::malloc_(&p[i], want));
-        cap[i] = want;
-        return 0;
-    }
-};
-HapBuffers& hap_bufs()
-{
-    static HapBuffers b;
-    return b;
-}
-enum { HB_REF = 0, HB_READ_OFF, HB_CODE, HB_PATH_OFF, HB_NSEG, HB_PATH, HB_POS, HB_LOW, HB_FWD, HB_OBS_OFF, HB_OBS, HB_REGIONS, HB_STATE, HB_RECS, HB_SEQ, HB_SUPPORT,
-       HB_QUERY_OFF, HB_SCRATCH };
-
 } // namespace
 
 extern "C" {
@@ -902,52 +877,40 @@ int sk_region_haplotypes(const char* ref_seq, int32_t ref_offset, int32_t ref_le
     SkContext& ctx = sk_ctx();
     SK_HIP(skrt::setDevice(ctx.device));
     hipStream_t st = ctx.stream;
-    HapBuffers& B = hap_bufs();
-    const size_t nr = size_t(n_reads), ng = size_t(n_regions);
+    const size_t nr = size_t(n_reads), ng = size_t(n_regions), no = n_reads > 0 ? nr + 1 : 0; // (nothing of the reads' arrays goes up without reads)
     const size_t scratch_bytes = sk_region_haplotypes_scratch_bytes(n_reads, n_regions, seq_bound, support_bound);
-    if (B.reserve(HB_REF, size_t(ref_len) + 16) || B.reserve(HB_READ_OFF, 8 * (nr + 1)) || B.reserve(HB_CODE, size_t(n_bases) + 16) || B.reserve(HB_PATH_OFF, 8 * (nr + 1)) ||
-        B.reserve(HB_NSEG, 4 * nr + 16) || B.reserve(HB_PATH, sizeof(sk_path_seg) * size_t(n_segs) + 16) || B.reserve(HB_POS, 4 * nr + 16) || B.reserve(HB_LOW, nr + 16) ||
-        B.reserve(HB_FWD, nr + 16) || B.reserve(HB_OBS_OFF, 8 * (nr + 1)) || B.reserve(HB_OBS, sizeof(sk_intake_obs) * size_t(n_obs) + 16) ||
-        B.reserve(HB_REGIONS, sizeof(sk_active_region) * ng + 16) || B.reserve(HB_STATE, 256) || B.reserve(HB_RECS, sizeof(sk_region_haplotypes_rec) * ng + 16) ||
-        B.reserve(HB_SEQ, size_t(seq_bound) + 16) || B.reserve(HB_SUPPORT, 4 * size_t(support_bound) + 16) ||
-        B.reserve(HB_QUERY_OFF, 8 * (size_t(SK_HAP_MAX_SELECTED) * ng + 1)) || B.reserve(HB_SCRATCH, scratch_bytes + 16))
+    struct
+    {
+        char* ref; int64_t* read_off; uint8_t* code; int64_t* path_off; int32_t* n_seg; sk_path_seg* path; int32_t* pos; uint8_t* low; uint8_t* fwd;
+        int64_t* obs_off; sk_intake_obs* obs; sk_active_region* regions; int32_t* n_regions; sk_region_haplotypes_rec* recs; uint8_t* seq; int32_t* support;
+        int64_t* query_off; char* scratch; int64_t* totals;
+    } d;
+    int rc = 0;
+    // (+ 16 bytes and the like: kernels read whole words past an array's end; every piece starts at a multiple of 256 bytes, which the
+    // scratch's 16-byte alignment needs; sk_region_haplotypes_dev and sk_check_device_errors reserve nothing of the arena)
+    if (sk_carve(d, [&](SkArena& ar) {
+            return decltype(d){ ar.up(ref_seq, size_t(ref_len), 16, st, rc), ar.up(read_off, no, 1, st, rc), ar.up(read_code, size_t(n_bases), 16, st, rc),
+                                ar.up(path_off, no, 1, st, rc), ar.up(n_seg, nr, 4, st, rc), ar.up(path, size_t(n_segs), 2, st, rc), ar.up(pos, nr, 4, st, rc),
+                                ar.up(low_mapq, nr, 16, st, rc), ar.up(is_fwd_strand, nr, 16, st, rc), ar.up(obs_off, no, 1, st, rc),
+                                ar.up(obs, size_t(n_obs), 1, st, rc), ar.up(regions, ng, 2, st, rc), ar.up(&n_regions, 1, 0, st, rc),
+                                ar.take<sk_region_haplotypes_rec>(ng + 1), ar.take<uint8_t>(size_t(seq_bound) + 16), ar.take<int32_t>(size_t(support_bound) + 4),
+                                ar.take<int64_t>(size_t(SK_HAP_MAX_SELECTED) * ng + 1), ar.take<char>(scratch_bytes + 16), ar.take<int64_t>(3) };
+        }) || rc)
         return 1;
-    if (ref_len > 0) SK_HIP(skrt::memcpyAsync(B.p[HB_REF], ref_seq, size_t(ref_len), hipMemcpyHostToDevice, st));
-    if (n_reads > 0) {
-        SK_HIP(skrt::memcpyAsync(B.p[HB_READ_OFF], read_off, 8 * (nr + 1), hipMemcpyHostToDevice, st));
-        if (n_bases) SK_HIP(skrt::memcpyAsync(B.p[HB_CODE], read_code, size_t(n_bases), hipMemcpyHostToDevice, st));
-        SK_HIP(skrt::memcpyAsync(B.p[HB_PATH_OFF], path_off, 8 * (nr + 1), hipMemcpyHostToDevice, st));
-        SK_HIP(skrt::memcpyAsync(B.p[HB_NSEG], n_seg, 4 * nr, hipMemcpyHostToDevice, st));
-        if (n_segs) SK_HIP(skrt::memcpyAsync(B.p[HB_PATH], path, sizeof(sk_path_seg) * size_t(n_segs), hipMemcpyHostToDevice, st));
-        SK_HIP(skrt::memcpyAsync(B.p[HB_POS], pos, 4 * nr, hipMemcpyHostToDevice, st));
-        SK_HIP(skrt::memcpyAsync(B.p[HB_LOW], low_mapq, nr, hipMemcpyHostToDevice, st));
-        SK_HIP(skrt::memcpyAsync(B.p[HB_FWD], is_fwd_strand, nr, hipMemcpyHostToDevice, st));
-        SK_HIP(skrt::memcpyAsync(B.p[HB_OBS_OFF], obs_off, 8 * (nr + 1), hipMemcpyHostToDevice, st));
-        if (n_obs) SK_HIP(skrt::memcpyAsync(B.p[HB_OBS], obs, sizeof(sk_intake_obs) * size_t(n_obs), hipMemcpyHostToDevice, st));
-    }
-    if (n_regions > 0) SK_HIP(skrt::memcpyAsync(B.p[HB_REGIONS], regions, sizeof(sk_active_region) * ng, hipMemcpyHostToDevice, st));
-    char* state_block = static_cast<char*>(B.p[HB_STATE]); // n_regions, then the totals
-    int32_t* d_n = reinterpret_cast<int32_t*>(state_block);
-    int64_t* d_totals = reinterpret_cast<int64_t*>(state_block + 64);
-    SK_HIP(skrt::memcpyAsync(d_n, &n_regions, sizeof(int32_t), hipMemcpyHostToDevice, st));
-    if (sk_region_haplotypes_dev(static_cast<char*>(B.p[HB_REF]), ref_offset, ref_len, n_reads, static_cast<int64_t*>(B.p[HB_READ_OFF]), static_cast<uint8_t*>(B.p[HB_CODE]),
-                                 static_cast<int64_t*>(B.p[HB_PATH_OFF]), static_cast<int32_t*>(B.p[HB_NSEG]), static_cast<sk_path_seg*>(B.p[HB_PATH]),
-                                 static_cast<int32_t*>(B.p[HB_POS]), static_cast<uint8_t*>(B.p[HB_LOW]), static_cast<uint8_t*>(B.p[HB_FWD]),
-                                 static_cast<int64_t*>(B.p[HB_OBS_OFF]), static_cast<sk_intake_obs*>(B.p[HB_OBS]), max_indel_size, buf_begin, buf_end, ploidy,
-                                 static_cast<sk_active_region*>(B.p[HB_REGIONS]), d_n, n_regions, static_cast<sk_region_haplotypes_rec*>(B.p[HB_RECS]),
-                                 static_cast<uint8_t*>(B.p[HB_SEQ]), seq_bound, static_cast<int32_t*>(B.p[HB_SUPPORT]), support_bound,
-                                 static_cast<int64_t*>(B.p[HB_QUERY_OFF]), d_totals, B.p[HB_SCRATCH], scratch_bytes, st))
+    if (sk_region_haplotypes_dev(d.ref, ref_offset, ref_len, n_reads, d.read_off, d.code, d.path_off, d.n_seg, d.path, d.pos, d.low, d.fwd, d.obs_off, d.obs,
+                                 max_indel_size, buf_begin, buf_end, ploidy, d.regions, d.n_regions, n_regions, d.recs, d.seq, seq_bound, d.support, support_bound,
+                                 d.query_off, d.totals, d.scratch, scratch_bytes, st))
         return 1;
     int64_t t[3] = { 0, 0, 0 };
-    SK_HIP(skrt::memcpyAsync(t, d_totals, sizeof(t), hipMemcpyDeviceToHost, st));
-    if (n_regions > 0) SK_HIP(skrt::memcpyAsync(recs, B.p[HB_RECS], sizeof(sk_region_haplotypes_rec) * ng, hipMemcpyDeviceToHost, st));
+    SK_HIP(skrt::memcpyAsync(t, d.totals, sizeof(t), hipMemcpyDeviceToHost, st));
+    if (n_regions > 0) SK_HIP(skrt::memcpyAsync(recs, d.recs, sizeof(sk_region_haplotypes_rec) * ng, hipMemcpyDeviceToHost, st));
     SK_HIP(skrt::streamSynchronize(st));
     if (sk_check_device_errors()) return 1;
     if (t[0] < 0 || t[0] > int64_t(SK_HAP_MAX_SELECTED) * n_regions || t[1] < 0 || t[1] > seq_bound || t[2] < 0 || t[2] > support_bound)
         return sk_fail("sk_region_haplotypes: totals out of range");
-    SK_HIP(skrt::memcpyAsync(query_off, B.p[HB_QUERY_OFF], 8 * size_t(t[0] + 1), hipMemcpyDeviceToHost, st));
-    if (t[1] > 0) SK_HIP(skrt::memcpyAsync(seq_pool, B.p[HB_SEQ], size_t(t[1]), hipMemcpyDeviceToHost, st));
-    if (t[2] > 0) SK_HIP(skrt::memcpyAsync(support_pool, B.p[HB_SUPPORT], 4 * size_t(t[2]), hipMemcpyDeviceToHost, st));
+    SK_HIP(skrt::memcpyAsync(query_off, d.query_off, 8 * size_t(t[0] + 1), hipMemcpyDeviceToHost, st));
+    if (t[1] > 0) SK_HIP(skrt::memcpyAsync(seq_pool, d.seq, size_t(t[1]), hipMemcpyDeviceToHost, st));
+    if (t[2] > 0) SK_HIP(skrt::memcpyAsync(support_pool, d.support, 4 * size_t(t[2]), hipMemcpyDeviceToHost, st));
     SK_HIP(skrt::streamSynchronize(st));
     for (int q = 0; q < 3; ++q) totals[q] = t[q];
     return 0;

@@ -691,6 +691,9 @@ extern "C" int sk_score_alignments_dev_generic(const sk_align_batch* b, double* 
     return 0;
 }
 
+static SkDevBuf g_extra; // sk_score_alignments' column form (outside the arena's reservation: sized only after it)
+void sk_score_extra_reset() { g_extra.drop(); }
+
 extern "C" int sk_score_alignments(const sk_align_batch* hb, double* out_lnp)
 {
     SK_REQUIRE_INIT();
@@ -808,20 +811,8 @@ extern "C" int sk_score_alignments(const sk_align_batch* hb, double* out_lnp)
         }
         const size_t words = size_t(src_off[n]), nm = size_t(n) * size_t(d.evmask_words);
         // (outside the arena's first reservation: sized only now)
-        static thread_local struct Extra
-        {
-            void* p = nullptr;
-            size_t cap = 0;
-        } extra;
-        const size_t need_extra = sk_align256(4 * (words + 1)) + sk_align256(8 * size_t(n + 1)) + sk_align256(4 * (nm + 1));
-        if (extra.cap < need_extra) {
-            if (extra.p) (void)skrt::free_(extra.p);
-            extra.p = nullptr;
-            extra.cap = 0;
-            SK_HIP(skrt::malloc_(&extra.p, need_extra + need_extra / 4));
-            extra.cap = need_extra + need_extra / 4;
-        }
-        char* base = static_cast<char*>(extra.p);
+        if (g_extra.reserve(sk_align256(4 * (words + 1)) + sk_align256(8 * size_t(n + 1)) + sk_align256(4 * (nm + 1)))) return 1;
+        char* base = g_extra.as<char>();
         uint32_t* pc = reinterpret_cast<uint32_t*>(base);
         int64_t* po = reinterpret_cast<int64_t*>(base + sk_align256(4 * (words + 1)));
         uint32_t* pa = reinterpret_cast<uint32_t*>(base + sk_align256(4 * (words + 1)) + sk_align256(8 * size_t(n + 1)));

@@ -5,9 +5,61 @@
 
 #include "sk_rt.h"
 
+#include <atomic>
 #include <cstdint>
 #include <cstring>
 #include <string>
+
+void sk_set_error(const std::string& msg);
+int sk_fail(const std::string& msg);
+
+#define SK_HIP(expr)                                                                                          \
+    do {                                                                                                      \
+        hipError_t _e = (expr);                                                                               \
+        if (_e != hipSuccess) return sk_fail(std::string(#expr) + ": " + skrt::errorString(_e));              \
+    } while (0)
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The library's one grow-on-demand block of device (or page-locked host) memory.  State that outlives a call lives in named members of
+// this type and is dropped by its module's reset function at sk_shutdown (below); a host-buffer entry point's per-call arrays come from
+// the context arena (SkArena).  Nothing is freed at process exit: the runtime may be gone by then.
+// ---------------------------------------------------------------------------------------------------------------------
+extern std::atomic<int64_t> sk_grown_bytes[2]; // what the process's SkBufs hold: [0] device, [1] page-locked (sk_debug_grown_bytes)
+
+template <bool PINNED>
+struct SkBuf
+{
+    void* p = nullptr;
+    size_t cap = 0;
+    /// room for `bytes`; a block that grows is not copied, and grows to bytes + bytes / 4 + 4096 (a pileup stream asks for half: headroom_div 2)
+    int reserve(const size_t bytes, const size_t headroom_div = 4)
+    {
+        if (bytes <= cap) return 0;
+        drop();
+        const size_t want = bytes + bytes / headroom_div + 4096;
+        SK_HIP(PINNED ? skrt::hostMalloc(&p, want) : skrt::malloc_(&p, want));
+        cap = want;
+        sk_grown_bytes[PINNED] += int64_t(want);
+        return 0;
+    }
+    void drop()
+    {
+        if (p) (void)(PINNED ? skrt::hostFree(p) : skrt::free_(p));
+        sk_grown_bytes[PINNED] -= int64_t(cap);
+        p = nullptr;
+        cap = 0;
+    }
+    template <typename T> T* as() const { return static_cast<T*>(p); }
+};
+using SkDevBuf = SkBuf<false>;
+using SkPinBuf = SkBuf<true>;
+
+// what sk_shutdown calls, one per module with state that outlives a call: each drops its buffers and clears what points into them
+void sk_enum_reset();         // read_enumerate.hip: the job's buffers; the last run's candidate alignments and scores are forgotten
+void sk_feed_reset();         // bam_feed.hip: the feed's buffers and its kept stream
+void sk_deflate_reset();      // bgzf_deflate.hip: slots, tokens, slot lengths
+void sk_score_extra_reset();  // score_alignments.hip: the legacy batch's extra block
+void sk_stage_reset();        // sk_context.hip: SkStage's page-locked mirrors
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Device-resident tables.  Every value is computed ON THE HOST with the host libm, using the reference's own
@@ -52,9 +104,7 @@ struct SkContext
     SkTables host_tables;
     SkTables* dev_tables = nullptr;
     hipStream_t stream = nullptr; // used by the host-buffer entry points
-    // staging arena for the host-buffer entry points (grown on demand, never shrunk)
-    void* arena = nullptr;
-    size_t arena_bytes = 0;
+    SkDevBuf arena;               // staging arena for the host-buffer entry points (grown on demand, never shrunk; dropped by sk_shutdown)
     // sticky error bits raised by kernels on input the reference would have thrown on (sk_check_device_errors)
     unsigned* dev_error_flags = nullptr;
     // per-kernel attributes raised on this context's device (cleared with the context: another device starts from the defaults)
@@ -77,15 +127,6 @@ size_t sk_ga_ptr_bytes(int64_t grid, int max_query_len, int max_ref_len);
 int sk_ga_launch_counted(const sk_global_align_batch& dev_batch, const int32_t* dev_n, int64_t grid, int max_query_len, int max_ref_len, const sk_align_scores& sc,
                          int32_t* dev_out_score, int32_t* dev_out_begin_pos, sk_path_seg* dev_out_path, int32_t* dev_out_n_seg, sk_path_seg* dev_tmp_path,
                          uint8_t* dev_ptr_scratch, hipStream_t st);
-void sk_set_error(const std::string& msg);
-int sk_fail(const std::string& msg);
-
-#define SK_HIP(expr)                                                                                          \
-    do {                                                                                                      \
-        hipError_t _e = (expr);                                                                               \
-        if (_e != hipSuccess) return sk_fail(std::string(#expr) + ": " + skrt::errorString(_e));              \
-    } while (0)
-
 #define SK_REQUIRE_INIT()                                                                    \
     do {                                                                                     \
         if (!sk_ctx().ready) return sk_fail("strelka_amd: sk_init() has not succeeded");     \
@@ -101,9 +142,30 @@ struct SkArena
     {
         size_t off = (used + 255) & ~size_t(255);
         used = off + n * sizeof(T);
-        return reinterpret_cast<T*>(base + off);
+        return base ? reinterpret_cast<T*>(base + off) : nullptr; // (no base: a dry arena, which only counts -- sk_carve)
+    }
+    /// take<T>(n + slack_elems) with the first n elements on their way up from `src`; a failed copy leaves its error in rc
+    template <typename T> T* up(const T* src, const size_t n, const size_t slack_elems, hipStream_t st, int& rc)
+    {
+        T* d = take<T>(n + slack_elems);
+        if (!d || n == 0 || rc) return d;
+        const hipError_t e = skrt::memcpyAsync(d, src, n * sizeof(T), hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) rc = sk_fail(std::string("memcpyAsync (host to arena): ") + skrt::errorString(e));
+        return d;
     }
 };
+
+// An entry point states each of its device arrays once, in a function `carve(SkArena&)` that takes or ups them and returns a struct of
+// typed device pointers: run on a dry arena to learn the room, then, with that much reserved, for real.  The caller holds the arena until
+// it returns and calls nothing that reserves it again.
+template <typename P, typename F> int sk_carve(P& out, F&& carve)
+{
+    SkArena ar;
+    (void)carve(ar);
+    if (ar.reserve(ar.used)) return 1;
+    out = carve(ar);
+    return 0;
+}
 
 static inline size_t sk_align256(size_t n) { return (n + 255) & ~size_t(255); }
 

@@ -118,6 +118,8 @@ void build_tables(SkTables& t)
 }
 } // namespace
 
+std::atomic<int64_t> sk_grown_bytes[2];
+
 SkContext& sk_ctx() { return g_ctx; }
 void sk_set_error(const std::string& msg) { g_last_error = msg; }
 int sk_fail(const std::string& msg)
@@ -128,18 +130,10 @@ int sk_fail(const std::string& msg)
 
 int SkArena::reserve(size_t bytes)
 {
-    SkContext& c = sk_ctx();
-    bytes = sk_align256(bytes) + 4096;
-    if (c.arena_bytes < bytes) {
-        if (c.arena) (void)skrt::free_(c.arena);
-        c.arena = nullptr;
-        c.arena_bytes = 0;
-        size_t want = bytes + bytes / 4;
-        SK_HIP(skrt::malloc_(&c.arena, want));
-        c.arena_bytes = want;
-    }
-    base = static_cast<char*>(c.arena);
-    cap = c.arena_bytes;
+    SkDevBuf& a = sk_ctx().arena;
+    if (a.reserve(sk_align256(bytes) + 4096)) return 1;
+    base = a.as<char>();
+    cap = a.cap;
     used = 0;
     return 0;
 }
@@ -151,28 +145,13 @@ __global__ __launch_bounds__(256) void stage_copy_kernel(const uint4* __restrict
 {
     for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n16; i += gridDim.x * 256) dst[i] = src[i];
 }
-struct StageMirrors // the context's page-locked mirrors of SkStage's two blocks
-{
-    void* in = nullptr;
-    void* out = nullptr;
-    size_t in_cap = 0, out_cap = 0;
-};
-StageMirrors& stage_mirrors()
-{
-    static StageMirrors m;
-    return m;
+SkPinBuf g_stage_in, g_stage_out; // the context's page-locked mirrors of SkStage's two blocks
 }
-int grow_pinned(void*& p, size_t& cap, const size_t bytes)
+
+void sk_stage_reset()
 {
-    if (bytes <= cap) return 0;
-    if (p) (void)skrt::hostFree(p);
-    p = nullptr;
-    cap = 0;
-    const size_t want = bytes + bytes / 4 + 4096;
-    SK_HIP(skrt::hostMalloc(&p, want));
-    cap = want;
-    return 0;
-}
+    g_stage_in.drop();
+    g_stage_out.drop();
 }
 
 int SkStage::begin(const size_t in_bytes, const size_t out_bytes, const size_t extra_bytes, const int n_arrays)
@@ -180,11 +159,10 @@ int SkStage::begin(const size_t in_bytes, const size_t out_bytes, const size_t e
     skrt::wakeHint(); // (the caller fills the in block next)
     const size_t pad = 256 * size_t(n_arrays + 2);
     const size_t in_room = sk_align256(in_bytes + pad), out_room = sk_align256(out_bytes + pad);
-    StageMirrors& m = stage_mirrors();
-    if (grow_pinned(m.in, m.in_cap, in_room) || grow_pinned(m.out, m.out_cap, out_room)) return 1;
+    if (g_stage_in.reserve(in_room) || g_stage_out.reserve(out_room)) return 1;
     if (ar.reserve(in_room + out_room + extra_bytes + 256 * size_t(n_arrays + 2))) return 1;
-    h_in = static_cast<char*>(m.in);
-    h_out = static_cast<char*>(m.out);
+    h_in = g_stage_in.as<char>();
+    h_out = g_stage_out.as<char>();
     in_cap = in_room;
     out_cap = out_room;
     in_used = out_used = 0;
@@ -380,12 +358,18 @@ void sk_shutdown(void)
     SkContext& c = g_ctx;
     if (!c.ready) return;
     (void)skrt::setDevice(c.device);
+    // Nothing of the library's points into this device's memory afterwards: work in flight ends, then every module with state that outlives
+    // a call drops it (pileup stream and caller handles are the caller's, destroyed before this).  A broker client keeps its connection.
+    if (c.stream) (void)skrt::streamSynchronize(c.stream);
+    sk_enum_reset();
+    sk_feed_reset();
+    sk_deflate_reset();
+    sk_score_extra_reset();
+    sk_stage_reset();
+    c.arena.drop();
     if (c.stream && !skrt::remote()) (void)hipStreamDestroy(c.stream);
     if (c.dev_tables) (void)skrt::free_(c.dev_tables);
     if (c.dev_error_flags) (void)skrt::free_(c.dev_error_flags);
-    if (c.arena) (void)skrt::free_(c.arena);
-    // (a broker client keeps its connection: the process's grown buffers -- the job's, the streams', the staged calls' -- stay valid
-    // across sk_shutdown / sk_init as they do in a process with a context of its own; the broker frees them when the process ends)
     c = SkContext();
 }
 
@@ -409,6 +393,12 @@ int sk_check_device_errors(void)
     if (flags & SK_DEVERR_ALLELES)
         return sk_fail("sk_region_alleles_dev: a haplotype record outside the sequence pool or with more than two alternates, a counted region of no or more than 250 positions, or a capacity below its bound");
     return sk_fail("strelka_amd: a kernel reported an error");
+}
+
+void sk_debug_grown_bytes(int64_t* device_bytes, int64_t* pinned_bytes)
+{
+    if (device_bytes) *device_bytes = sk_grown_bytes[0];
+    if (pinned_bytes) *pinned_bytes = sk_grown_bytes[1];
 }
 
 int sk_debug_force_device_libm(int on)
