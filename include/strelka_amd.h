@@ -1258,8 +1258,8 @@ size_t sk_read_intake_scratch_bytes(int32_t n_reads, int64_t n_path_segments, in
  *             (candidate?, depth zero?, anchor?) per position -> active regions.
  *
  * On one stream sk_read_intake_dev -> sk_ref_anchors_dev -> sk_active_regions_dev run with no host copy in between.
- * Out of scope: closeActiveRegionDetector (:413-, it needs the read buffer's range; the caller's, from state_out), the multi-sample
- * synchroniser (ActiveRegionDetector::updateEndPosition, processExistingActiveRegion, closeActiveRegion), external or forced
+ * closeActiveRegionDetector (:413-440) and the multi-sample synchroniser (ActiveRegionDetector::updateEndPosition,
+ * processExistingActiveRegion, closeActiveRegion) are sk_sync_active_regions[_dev] (below).  Out of scope: external or forced
  * candidates (callers may edit is_candidate and sites before the walk), getReadSegments.
  * ---------------------------------------------------------------------------------------------------------------- */
 #define SK_REPEAT_MAX_UNIT 50
@@ -1306,6 +1306,92 @@ int sk_active_regions_dev(int32_t win_begin, int32_t n_pos, const sk_intake_site
                           sk_active_region* dev_regions, int64_t region_cap, int32_t* dev_n_regions, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Synchronised active regions (DESIGN section 8 item 1 (c')): ActiveRegionDetector (L/starling_common/ActiveRegionDetector.cpp), which
+ * stands between every sample's SampleActiveRegionDetector and the ActiveRegionProcessors -- for one sample too.
+ *
+ *   the call     updateEndPosition(pos) :77-89: processExistingActiveRegion(pos) first, then sample 0 .. S - 1 each take the step
+ *                sk_active_regions takes, and each region a sample returns is merged as it comes (updateActiveRegionRange :119-131:
+ *                _synchronizedActiveRegion.end_pos() == 0 reads as "none"; merge_range takes min begin and max end, so a sample's second
+ *                region can merge into its own first).
+ *   the close    processExistingActiveRegion :133-154: at a call pos >= end + MaxAssemblyPadding (9), unless some sample's raw
+ *                _activeRegionStartPos -- whatever its _numVariants; 0 right after createActiveRegion :325 -- is >= 0 and < end - 1.
+ *                closeActiveRegion :203-250: the assertion size() > 0; per sample max(ploidy(begin), ploidy(end - 1)) (getPloidy :280-293);
+ *                setPosToActiveRegionIdMap :267-278 (nothing for more than MaxRefSpanToBypassAssembly = 250 positions);
+ *                _prevActiveRegionEnd = end; the range cleared to begin = end = 0.
+ *   clear()      :98-111: closeActiveRegionDetector per sample (:413-440, its three branches; clearCoordinates leaves _isBeginning
+ *                alone), merged as it comes, then the close without a test.
+ *
+ * Every sample's repeat finder is given the same calls over the same reference, so one is_anchor array serves all samples.  The marks
+ * stand for _posToPloidyMap as it is when the regions close; marks the caller has erased (clearReadBuffer's eraseTo) are the
+ * caller's business.  The read buffer's end at a close is that call's pos: setEndPos(pos + 1) (:339) runs in the samples' steps, after
+ * processExistingActiveRegion(pos), and the call before left it at pos -- hence sk_region_params.buf_end = closed_at, which is the range
+ * the bypass test of ActiveRegionProcessor.cpp:48-49 sees.  prev_end of record i + 1 is end of record i, and of record 0 the state's: what
+ * sk_region_alleles[_dev] derives from prev_end_in and the region list.
+ *
+ * On one stream sk_read_intake_dev (per sample) -> sk_ref_anchors_dev -> sk_sync_active_regions_dev -> sk_sync_region_params_dev ->
+ * sk_region_haplotypes_params_dev -> sk_region_alleles_dev run with no host copy in between.  Out of scope: routing into the caller;
+ * what closeActiveRegion does beyond the list (filterOutConflictingForcedIndels, the somatic branch); clearReadBuffer / eraseTo
+ * bookkeeping; more than SK_MAX_SAMPLES samples.
+ * ---------------------------------------------------------------------------------------------------------------- */
+#define SK_SYNC_CLOSED_AT_CLEAR (-1) /* sk_sync_region.closed_at of a region clear() closed */
+typedef struct sk_ploidy_mark { /* one entry of a sample's _posToPloidyMap (updatePloidy :330-334) */
+    int32_t pos, ploidy;
+} sk_ploidy_mark;
+typedef struct sk_sync_state {
+    sk_ar_state sample[SK_MAX_SAMPLES]; /* the first n_samples are the call's; the others pass through */
+    int32_t sync_begin, sync_end;       /* _synchronizedActiveRegion; end 0: none (known_pos_range2::clear) */
+    int32_t prev_end;                   /* _prevActiveRegionEnd, initially -1 (ActiveRegionDetector.hh:117) */
+    uint32_t sample_mask;               /* the samples whose own detector contributed to the open region */
+} sk_sync_state;
+/** Every sample's sk_ar_state_initial, no synchronised region, prev_end = -1. */
+void sk_sync_state_initial(sk_sync_state* s);
+typedef struct sk_sync_region { /* one closeActiveRegion */
+    int32_t begin, end;
+    int32_t closed_at;                  /* the pos argument of the call whose processExistingActiveRegion closed it, or SK_SYNC_CLOSED_AT_CLEAR */
+    int32_t prev_end;                   /* the _prevActiveRegionEnd its processors were given */
+    uint8_t ploidy[SK_MAX_SAMPLES];     /* getPloidy(sample, region) for the call's samples, 0 for the others */
+    uint32_t sample_mask;               /* the samples whose own detector contributed a region */
+    uint32_t pad;
+} sk_sync_region;
+typedef struct sk_region_params { /* what one region's ActiveRegionProcessor of one sample is given besides the region */
+    int32_t buf_begin, buf_end; /* _readBuffer.getBeginPos() / getEndPos() when it runs */
+    int32_t ploidy, pad;
+} sk_region_params;
+/** Room for the regions a window of n_pos positions can close: n_pos + 1.  A call closes at most one region -- processExistingActiveRegion
+ *  runs once per call, and whatever the samples' steps merge afterwards waits for a later call's test -- and clear() closes at most one.
+ *  Host arithmetic only (works without a device); -1 for a negative count. */
+int64_t sk_sync_regions_bound(int32_t n_pos);
+/** The calls ActiveRegionDetector::updateEndPosition(pos) for pos = win_begin + 1 .. win_begin + n_pos over n_samples samples, then clear()
+ *  where do_clear != 0.  sites[n_samples][n_pos], is_candidate[n_samples][n_pos] as sk_read_intake leaves them per sample; is_anchor[n_pos]
+ *  as sk_ref_anchors does; marks[mark_off[s] .. mark_off[s + 1]) sample s's ploidy marks, positions ascending (mark_off[n_samples + 1]);
+ *  buf_begin[n_samples] / buf_end[n_samples]: every sample's _readBuffer.getBeginPos() / getEndPos() at clear(), read only where do_clear.
+ *  regions[0 .. *n_regions) in closing order; region_id (NULL: not wanted) [n_pos]: begin of the last closed region of this call of at
+ *  most 250 positions that covers win_begin + i, else -1 -- what the call adds to _posToActiveRegionIdMap, positions outside the window
+ *  dropped.  Windows chain through state_in / state_out (they may be the same object).  Refused with a message: n_samples outside
+ *  1..SK_MAX_SAMPLES, region_cap below sk_sync_regions_bound(n_pos), win_begin < 0, negative sizes, marks not ascending, a ploidy other
+ *  than 1 or 2; where createActiveRegion's assertion (:318) or closeActiveRegion's (:206) would fire the call fails and emits nothing. */
+int sk_sync_active_regions(int32_t n_samples, int32_t win_begin, int32_t n_pos, const sk_intake_site* sites, const uint8_t* is_candidate,
+                           const uint8_t* is_anchor, const int32_t* mark_off, const sk_ploidy_mark* marks, int32_t default_ploidy,
+                           const sk_sync_state* state_in, sk_sync_state* state_out, int32_t do_clear, const int32_t* buf_begin, const int32_t* buf_end,
+                           sk_sync_region* regions, int64_t region_cap, int32_t* n_regions, int32_t* region_id);
+/** The same on device memory (buf_begin / buf_end are read on the host); only enqueues.  Where an assertion would fire, or the marks are
+ *  not ascending or hold a ploidy other than 1 or 2, the sticky device flag is raised (sk_check_device_errors), n_regions is 0, region_id
+ *  is all -1 and state_out = state_in. */
+int sk_sync_active_regions_dev(int32_t n_samples, int32_t win_begin, int32_t n_pos, const sk_intake_site* dev_sites, const uint8_t* dev_is_candidate,
+                               const uint8_t* dev_is_anchor, const int32_t* dev_mark_off, const sk_ploidy_mark* dev_marks, int32_t default_ploidy,
+                               const sk_sync_state* dev_state_in, sk_sync_state* dev_state_out, int32_t do_clear, const int32_t* buf_begin,
+                               const int32_t* buf_end, sk_sync_region* dev_regions, int64_t region_cap, int32_t* dev_n_regions, int32_t* dev_region_id,
+                               void* hip_stream);
+/** One sample's records for sk_region_haplotypes_params[_dev] from the synchronised list: regions[i] = (begin, end, made_at = closed_at)
+ *  (NULL: not wanted), params[i] = (buf_begin, closed_at -- buf_end_at_clear for a region clear() closed --, ploidy[sample]).  Refused
+ *  with a message: sample outside 0..SK_MAX_SAMPLES - 1, negative sizes. */
+int sk_sync_region_params(const sk_sync_region* sync_regions, int32_t n_regions, int32_t sample, int32_t buf_begin, int32_t buf_end_at_clear,
+                          sk_active_region* regions, sk_region_params* params);
+/** The same on device memory, dev_n_regions included (region_cap: the room of the three arrays); only enqueues. */
+int sk_sync_region_params_dev(const sk_sync_region* dev_sync_regions, const int32_t* dev_n_regions, int64_t region_cap, int32_t sample, int32_t buf_begin,
+                              int32_t buf_end_at_clear, sk_active_region* dev_regions, sk_region_params* dev_params, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Region haplotypes: what the detector keeps per read for haplotype generation, and what the reference
  * does with it first -- read segments, haplotype generation by counting, haplotype selection -- for every region of the list
  * sk_active_regions[_dev] leaves.
@@ -1336,7 +1422,8 @@ int sk_active_regions_dev(int32_t win_begin, int32_t n_pos, const sk_intake_site
  * On one stream sk_read_intake_dev -> sk_ref_anchors_dev -> sk_active_regions_dev -> sk_region_haplotypes_dev run with no host copy
  * in between.  Out of scope: routing the results into the caller; the assembly fallback (generateHaplotypesWithAssembly,
  * getReadSegments with partial reads) -- a region whose counting fails reports its status and the host does the rest;
- * doNotUseHaplotyping's IndelBuffer marks; _haplotypesToExclude; the multi-sample synchroniser; external and forced candidates.
+ * doNotUseHaplotyping's IndelBuffer marks; _haplotypesToExclude; external and forced candidates.  The multi-sample synchroniser's regions come
+ * through sk_region_haplotypes_params[_dev], one call per sample.
  * What a region does with its selected haplotypes -- the aligner, the walk, the records for the buffers -- is sk_region_alleles[_dev]
  * (below), chained on the same stream without a host copy.
  * ---------------------------------------------------------------------------------------------------------------- */
@@ -1393,15 +1480,35 @@ int sk_region_haplotypes_dev(const char* dev_ref_seq, int32_t ref_offset, int32_
                              const sk_active_region* dev_regions, const int32_t* dev_n_regions, int64_t region_cap, sk_region_haplotypes_rec* dev_recs,
                              uint8_t* dev_seq_pool, int64_t seq_cap, int32_t* dev_support_pool, int64_t support_cap, int64_t* dev_query_off,
                              int64_t* dev_totals, void* dev_scratch, size_t scratch_bytes, void* hip_stream);
+/** sk_region_haplotypes with the read buffer's range and the ploidy per region, params[n_regions]: the synchronised regions of one window
+ *  close at different times and carry different ploidies (sk_sync_region_params fills the records for one sample).  Records that are all
+ *  the same give sk_region_haplotypes' output byte for byte.  Refused with a message: what sk_region_haplotypes refuses, per region. */
+int sk_region_haplotypes_params(const char* ref_seq, int32_t ref_offset, int32_t ref_len, int32_t n_reads, const int64_t* read_off, const uint8_t* read_code,
+                                const int64_t* path_off, const int32_t* n_seg, const sk_path_seg* path, const int32_t* pos, const uint8_t* low_mapq,
+                                const uint8_t* is_fwd_strand, const int64_t* obs_off, const sk_intake_obs* obs, uint32_t max_indel_size,
+                                const sk_region_params* params, const sk_active_region* regions, int32_t n_regions, sk_region_haplotypes_rec* recs,
+                                uint8_t* seq_pool, int64_t seq_cap, int32_t* support_pool, int64_t support_cap, int64_t* query_off, int64_t* totals);
+/** The same on device memory, dev_params[region_cap] included; only enqueues.  A record with a ploidy other than 1 or 2 raises the sticky
+ *  device flag (sk_check_device_errors); its region's record is SK_HAP_BYPASSED with nothing selected. */
+int sk_region_haplotypes_params_dev(const char* dev_ref_seq, int32_t ref_offset, int32_t ref_len, int32_t n_reads, const int64_t* dev_read_off,
+                                    const uint8_t* dev_read_code, const int64_t* dev_path_off, const int32_t* dev_n_seg, const sk_path_seg* dev_path,
+                                    const int32_t* dev_pos, const uint8_t* dev_low_mapq, const uint8_t* dev_is_fwd_strand, const int64_t* dev_obs_off,
+                                    const sk_intake_obs* dev_obs, uint32_t max_indel_size, const sk_region_params* dev_params,
+                                    const sk_active_region* dev_regions, const int32_t* dev_n_regions, int64_t region_cap, sk_region_haplotypes_rec* dev_recs,
+                                    uint8_t* dev_seq_pool, int64_t seq_cap, int32_t* dev_support_pool, int64_t support_cap, int64_t* dev_query_off,
+                                    int64_t* dev_totals, void* dev_scratch, size_t scratch_bytes, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Region alleles: what an active region does to the rest of the program once its haplotypes are
  * selected -- ActiveRegionProcessor::processSelectedHaplotypes (L/starling_common/ActiveRegionProcessor.cpp:518-571),
  * discoverIndelsAndMismatches (:573-707) and processDiscoveredIndelsAndMismatches (:709-757) -- for every region of the list, from
- * what sk_region_haplotypes[_dev] leaves.  Single sample: _synchronizedActiveRegion is the region.
+ * what sk_region_haplotypes[_dev] leaves.  The region is _synchronizedActiveRegion: sk_sync_active_regions' list through
+ * sk_sync_region_params (for one sample whose detector makes no region before the last one closed, the sample's own list: recorded in
+ * tests/test_sync_regions_model.py).
  *
  *   prev_end     _prevActiveRegionEnd: prev_end_in for region 0, regions[i - 1].end afterwards (ActiveRegionDetector.cpp:248: it
- *                advances whatever became of the region before).
+ *                advances whatever became of the region before).  sk_sync_region.prev_end holds the same values: record 0's is the
+ *                sk_sync_state's prev_end, the caller's prev_end_in.
  *   alternates   the selected haplotypes with is_reference == 0, in selection order: at most two
  *                (selectOrDropHaplotypesWithSameCount, :486-516); haplotype_id 1 and 2 (:562-570).
  *   alignment    each alternate against _refSegment (the reference over [begin, end), 'N' outside the segment) with the detector's
@@ -1424,7 +1531,7 @@ int sk_region_haplotypes_dev(const char* dev_ref_seq, int32_t ref_offset, int32_
  * On one stream sk_read_intake_dev -> sk_ref_anchors_dev -> sk_active_regions_dev -> sk_region_haplotypes_dev ->
  * sk_region_alleles_dev run with no host copy in between.  Not routed into adapter/ yet.  Out of scope: routing;
  * addIndelObservation / addCandidateSnv themselves; the assembly fallback; doNotUseHaplotyping's marks; _haplotypesToExclude and the
- * somatic branch; the multi-sample synchroniser; filterOutConflictingForcedIndels.
+ * somatic branch; filterOutConflictingForcedIndels.
  * ---------------------------------------------------------------------------------------------------------------- */
 enum {
     SK_ALLELE_DECLINE_BEGIN_POS = 4, /* (after SK_HAP_DECLINE_*) the aligner's beginPos > 0 */

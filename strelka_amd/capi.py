@@ -234,6 +234,8 @@ EXPORTS = [
     "sk_bgzf_scan", "sk_bgzf_inflate", "sk_bgzf_inflate_prefixed", "sk_bgzf_inflate_dev", "sk_bgzf_deflate_bound", "sk_bgzf_deflate", "sk_bgzf_deflate_dev", "sk_bam_header_end", "sk_bam_scan_records", "sk_bam_decode", "sk_bam_decode_kept", "sk_bam_decode_dev", "sk_normalize_alignments", "sk_normalize_alignments_dev",
     "sk_intake_options_default", "sk_read_intake_obs_bound", "sk_read_intake", "sk_read_intake_dev", "sk_read_intake_scratch_bytes",
     "sk_ar_state_initial", "sk_ref_anchors", "sk_ref_anchors_dev", "sk_active_regions_bound", "sk_active_regions", "sk_active_regions_dev",
+    "sk_sync_state_initial", "sk_sync_regions_bound", "sk_sync_active_regions", "sk_sync_active_regions_dev", "sk_sync_region_params", "sk_sync_region_params_dev",
+    "sk_region_haplotypes_params", "sk_region_haplotypes_params_dev",
     "sk_region_haplotypes_seq_bound", "sk_region_haplotypes_support_bound", "sk_region_haplotypes_scratch_bytes", "sk_region_haplotypes", "sk_region_haplotypes_dev",
     "sk_region_alleles_allele_bound", "sk_region_alleles_insert_bound", "sk_region_alleles_scratch_bytes", "sk_region_alleles", "sk_region_alleles_dev", "sk_debug_region_alleles",
     "sk_align_builder_create", "sk_align_builder_destroy", "sk_align_builder_clear", "sk_align_builder_append", "sk_align_builder_add_read",
@@ -360,6 +362,15 @@ def lib():
         L.sk_ref_anchors_dev.argtypes = L.sk_ref_anchors.argtypes + [c_void_p]
         L.sk_active_regions.argtypes = [C.c_int32, C.c_int32] + [c_void_p] * 6 + [C.c_int64, c_void_p]
         L.sk_active_regions_dev.argtypes = L.sk_active_regions.argtypes + [c_void_p]
+        L.sk_sync_state_initial.argtypes = [c_void_p]
+        L.sk_sync_state_initial.restype = None
+        L.sk_sync_regions_bound.restype = C.c_int64
+        L.sk_sync_regions_bound.argtypes = [C.c_int32]
+        L.sk_sync_active_regions.argtypes = [C.c_int32, C.c_int32, C.c_int32] + [c_void_p] * 5 + [C.c_int32, c_void_p, c_void_p, C.c_int32, c_void_p, c_void_p, c_void_p,
+                                             C.c_int64, c_void_p, c_void_p]
+        L.sk_sync_active_regions_dev.argtypes = L.sk_sync_active_regions.argtypes + [c_void_p]
+        L.sk_sync_region_params.argtypes = [c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_void_p, c_void_p]
+        L.sk_sync_region_params_dev.argtypes = [c_void_p, c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_void_p, c_void_p, c_void_p]
         L.sk_region_haplotypes_seq_bound.restype = C.c_int64
         L.sk_region_haplotypes_seq_bound.argtypes = [C.c_int64]
         L.sk_region_haplotypes_support_bound.restype = C.c_int64
@@ -370,6 +381,10 @@ def lib():
                                            c_void_p, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, c_void_p]
         L.sk_region_haplotypes_dev.argtypes = [c_void_p, C.c_int32, C.c_int32, C.c_int32] + [c_void_p] * 10 + [C.c_uint32, C.c_int32, C.c_int32, C.c_int32, c_void_p, c_void_p,
                                                C.c_int64, c_void_p, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, c_void_p, c_void_p, C.c_size_t, c_void_p]
+        L.sk_region_haplotypes_params.argtypes = [c_void_p, C.c_int32, C.c_int32, C.c_int32] + [c_void_p] * 10 + [C.c_uint32, c_void_p, c_void_p, C.c_int32,
+                                                  c_void_p, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, c_void_p]
+        L.sk_region_haplotypes_params_dev.argtypes = [c_void_p, C.c_int32, C.c_int32, C.c_int32] + [c_void_p] * 10 + [C.c_uint32, c_void_p, c_void_p, c_void_p,
+                                                      C.c_int64, c_void_p, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, c_void_p, c_void_p, C.c_size_t, c_void_p]
         L.sk_region_alleles_allele_bound.restype = C.c_int64
         L.sk_region_alleles_allele_bound.argtypes = [C.c_int64, C.c_int32]
         L.sk_region_alleles_insert_bound.restype = C.c_int64
@@ -1582,6 +1597,96 @@ def active_regions(win_begin, sites, is_candidate, is_anchor, state=None, region
     return regions[:int(n_regions[0])], state_out
 
 
+MAX_SAMPLES = 8
+SYNC_CLOSED_AT_CLEAR = -1
+PLOIDY_MARK_DTYPE = np.dtype([("pos", "<i4"), ("ploidy", "<i4")])
+SYNC_STATE_DTYPE = np.dtype([("sample", AR_STATE_DTYPE, (MAX_SAMPLES,)), ("sync_begin", "<i4"), ("sync_end", "<i4"), ("prev_end", "<i4"), ("sample_mask", "<u4")])
+SYNC_REGION_DTYPE = np.dtype([("begin", "<i4"), ("end", "<i4"), ("closed_at", "<i4"), ("prev_end", "<i4"), ("ploidy", "u1", (MAX_SAMPLES,)), ("sample_mask", "<u4"),
+                              ("pad", "<u4")])
+REGION_PARAMS_DTYPE = np.dtype([("buf_begin", "<i4"), ("buf_end", "<i4"), ("ploidy", "<i4"), ("pad", "<i4")])
+assert SYNC_STATE_DTYPE.itemsize == 208 and SYNC_REGION_DTYPE.itemsize == 32 and REGION_PARAMS_DTYPE.itemsize == 16 and PLOIDY_MARK_DTYPE.itemsize == 8
+
+
+def sync_state_initial():
+    """ActiveRegionDetector's coordinates as its constructor leaves them -> SYNC_STATE_DTYPE[1]"""
+    s = np.zeros(1, SYNC_STATE_DTYPE)
+    lib().sk_sync_state_initial(_p(s))
+    return s
+
+
+def sync_state(values):
+    """dict(samples [dict of the six fields], sync_begin, sync_end, prev_end, sample_mask) -> SYNC_STATE_DTYPE[1]; samples beyond the
+    list are initial"""
+    s = sync_state_initial()
+    for k, d in enumerate(values["samples"]):
+        for f in AR_STATE_DTYPE.names:
+            s["sample"][0][k][f] = d[f]
+    for f in ("sync_begin", "sync_end", "prev_end", "sample_mask"):
+        s[f][0] = values[f]
+    return s
+
+
+def sync_state_dict(s, n_samples=MAX_SAMPLES):
+    """SYNC_STATE_DTYPE[1] -> the dict sync_state takes, of the first n_samples samples"""
+    return dict(samples=[{f: int(s["sample"][0][k][f]) for f in AR_STATE_DTYPE.names} for k in range(n_samples)], sync_begin=int(s["sync_begin"][0]),
+                sync_end=int(s["sync_end"][0]), prev_end=int(s["prev_end"][0]), sample_mask=int(s["sample_mask"][0]))
+
+
+def sync_regions_bound(n_pos):
+    """room for the regions a window of n_pos positions can close; host arithmetic, works without a device"""
+    return int(lib().sk_sync_regions_bound(int(n_pos)))
+
+
+def pack_ploidy_marks(marks, n_samples):
+    """[S][(pos, ploidy)] or None -> (mark_off int32[S + 1], PLOIDY_MARK_DTYPE[])"""
+    marks = marks if marks is not None else [[] for _ in range(n_samples)]
+    off = np.zeros(n_samples + 1, np.int32)
+    flat = []
+    for s in range(n_samples):
+        flat += [(int(p), int(v)) for p, v in marks[s]]
+        off[s + 1] = len(flat)
+    arr = np.zeros(len(flat) + 1, PLOIDY_MARK_DTYPE)
+    for k, m in enumerate(flat):
+        arr[k] = m
+    return off, arr
+
+
+def sync_active_regions(win_begin, sites, is_candidate, is_anchor, marks=None, default_ploidy=2, state=None, do_clear=False, buf_begin=None, buf_end=None,
+                        region_cap=None, want_region_id=True):
+    """sites: INTAKE_SITE_DTYPE[S][n_pos]; is_candidate [S][n_pos]; is_anchor [n_pos]; marks [S][(pos, ploidy)]; state: SYNC_STATE_DTYPE[1] or
+    None (the initial one) -> (regions SYNC_REGION_DTYPE[], state_out SYNC_STATE_DTYPE[1], region_id int32[n_pos] or None) through
+    sk_sync_active_regions"""
+    sites = np.ascontiguousarray(sites, INTAKE_SITE_DTYPE)
+    n_samples = len(sites)
+    n = len(np.asarray(is_anchor))
+    sites = sites.reshape(n_samples, n)
+    cand = np.ascontiguousarray(np.asarray(is_candidate).astype(np.uint8).reshape(n_samples, n))
+    anchor = np.ascontiguousarray(np.asarray(is_anchor).astype(np.uint8))
+    mark_off, mark_arr = pack_ploidy_marks(marks, n_samples)
+    state_in = sync_state_initial() if state is None else np.ascontiguousarray(state, SYNC_STATE_DTYPE)
+    state_out = np.zeros(1, SYNC_STATE_DTYPE)
+    cap = sync_regions_bound(n) if region_cap is None else int(region_cap)
+    regions = np.zeros(max(cap, 1), SYNC_REGION_DTYPE)
+    n_regions = np.zeros(1, np.int32)
+    region_id = np.full(max(n, 1), -2, np.int32) if want_region_id else None
+    bb = None if buf_begin is None else np.ascontiguousarray(buf_begin, np.int32)
+    be = None if buf_end is None else np.ascontiguousarray(buf_end, np.int32)
+    _check(lib().sk_sync_active_regions(n_samples, int(win_begin), n, _p(sites) if n else None, _p(cand) if n else None, _p(anchor) if n else None, _p(mark_off),
+                                        _p(mark_arr), int(default_ploidy), _p(state_in), _p(state_out), 1 if do_clear else 0, _p(bb), _p(be), _p(regions), cap,
+                                        _p(n_regions), _p(region_id)))
+    return regions[:int(n_regions[0])], state_out, None if region_id is None else region_id[:n]
+
+
+def sync_region_params(sync_regions, sample, buf_begin, buf_end_at_clear=0):
+    """SYNC_REGION_DTYPE[] -> (ACTIVE_REGION_DTYPE[], REGION_PARAMS_DTYPE[]) of one sample through sk_sync_region_params"""
+    sync = np.ascontiguousarray(sync_regions, SYNC_REGION_DTYPE)
+    m = len(sync)
+    regions = np.zeros(max(m, 1), ACTIVE_REGION_DTYPE)
+    params = np.zeros(max(m, 1), REGION_PARAMS_DTYPE)
+    _check(lib().sk_sync_region_params(_p(sync) if m else None, m, int(sample), int(buf_begin), int(buf_end_at_clear), _p(regions), _p(params)))
+    return regions[:m], params[:m]
+
+
 HAP_COUNTED, HAP_BYPASSED, HAP_NO_READS, HAP_TOO_FEW_COVERING, HAP_DECLINED = range(5)
 HAP_DECLINE_NONE, HAP_DECLINE_GROUPS, HAP_DECLINE_READ_INDEX_SPREAD, HAP_DECLINE_READ_SPAN = range(4)
 HAP_MAX_SELECTED = 3
@@ -1613,10 +1718,12 @@ def region_haplotype_records(recs, seq_pool, support_pool):
     return out
 
 
-def region_haplotypes(ref_seq, ref_offset, reads, low_mapq, is_fwd_strand, regions, buf_begin, buf_end, ploidy=2, intake=None, opt=None, raw=False):
+def region_haplotypes(ref_seq, ref_offset, reads, low_mapq, is_fwd_strand, regions, buf_begin, buf_end, ploidy=2, intake=None, opt=None, raw=False, params=None):
     """reads: the form read_intake takes; regions: ACTIVE_REGION_DTYPE[] or [(begin, end)]; intake: read_intake's result for these reads
     (computed here when None) -> per-region records with haplotype strings and support lists (region_haplotype_records) through
-    sk_region_haplotypes; raw=True: dict(recs, seq_pool, support_pool, query_off, totals) as the entry point leaves them"""
+    sk_region_haplotypes; raw=True: dict(recs, seq_pool, support_pool, query_off, totals) as the entry point leaves them.
+    params: REGION_PARAMS_DTYPE[] or [(buf_begin, buf_end, ploidy)] per region -- then through sk_region_haplotypes_params, and buf_begin,
+    buf_end and ploidy are not read"""
     L = lib()
     n = len(reads)
     opt = opt or intake_options()
@@ -1643,9 +1750,22 @@ def region_haplotypes(ref_seq, ref_offset, reads, low_mapq, is_fwd_strand, regio
     query_off = np.zeros(HAP_MAX_SELECTED * m + 1, np.int64)
     totals = np.zeros(3, np.int64)
     ref_b = ref_seq.encode() if isinstance(ref_seq, str) else bytes(ref_seq)
-    _check(L.sk_region_haplotypes(ref_b, int(ref_offset), len(ref_b), n, _p(read_off), _p(code), _p(path_off), _p(n_seg), _p(path), _p(pos), _p(low), _p(fwd),
-                                  _p(obs_off), _p(obs) if len(obs) else None, int(opt.max_indel_size), int(buf_begin), int(buf_end), int(ploidy),
-                                  _p(reg) if m else None, m, _p(recs), _p(seq_pool), seq_cap, _p(support_pool), support_cap, _p(query_off), _p(totals)))
+    if params is not None:
+        if isinstance(params, np.ndarray) and params.dtype == REGION_PARAMS_DTYPE:
+            par = np.ascontiguousarray(params)
+        else:
+            par = np.zeros(len(params), REGION_PARAMS_DTYPE)
+            for i, q in enumerate(params):
+                par[i] = (int(q[0]), int(q[1]), int(q[2]), 0)
+        assert len(par) == m
+        par = np.concatenate([par, np.zeros(1, REGION_PARAMS_DTYPE)])
+        _check(L.sk_region_haplotypes_params(ref_b, int(ref_offset), len(ref_b), n, _p(read_off), _p(code), _p(path_off), _p(n_seg), _p(path), _p(pos), _p(low), _p(fwd),
+                                             _p(obs_off), _p(obs) if len(obs) else None, int(opt.max_indel_size), _p(par), _p(reg) if m else None, m, _p(recs),
+                                             _p(seq_pool), seq_cap, _p(support_pool), support_cap, _p(query_off), _p(totals)))
+    else:
+        _check(L.sk_region_haplotypes(ref_b, int(ref_offset), len(ref_b), n, _p(read_off), _p(code), _p(path_off), _p(n_seg), _p(path), _p(pos), _p(low), _p(fwd),
+                                      _p(obs_off), _p(obs) if len(obs) else None, int(opt.max_indel_size), int(buf_begin), int(buf_end), int(ploidy),
+                                      _p(reg) if m else None, m, _p(recs), _p(seq_pool), seq_cap, _p(support_pool), support_cap, _p(query_off), _p(totals)))
     res = dict(recs=recs[:m], seq_pool=seq_pool[:int(totals[1])], support_pool=support_pool[:int(totals[2])], query_off=query_off[:int(totals[0]) + 1], totals=totals)
     return res if raw else region_haplotype_records(res["recs"], res["seq_pool"], res["support_pool"])
 

@@ -291,6 +291,317 @@ __global__ __launch_bounds__(AR_WALK_THREADS) void ar_walk_kernel(const int32_t 
     }
 }
 
+// ---- the multi-sample synchroniser (ActiveRegionDetector, .cpp:77-154, :203-293) -----------------------------------------------------------------
+
+enum { AR_SYNC_WORDS = 64, AR_SYNC_CHUNK = 64 * AR_SYNC_WORDS }; // (2 * SK_MAX_SAMPLES + 1) * 64 words: 8 704 bytes of LDS beside AR2's 6 144
+enum { AR_SYNC_PADDING = 9 };                                    // ActiveRegionReadBuffer::MaxAssemblyPadding
+enum { AR_SYNC_ID_THREADS = 256 };
+
+struct SyncArgs
+{
+    int32_t n_samples, win_begin, n_pos;
+    const sk_intake_site* sites; // [n_samples][n_pos]
+    const uint8_t* is_candidate; // [n_samples][n_pos]
+    const uint8_t* is_anchor;    // [n_pos]
+    const int32_t* mark_off;     // [n_samples + 1]
+    const sk_ploidy_mark* marks;
+    int32_t default_ploidy;
+    const sk_sync_state* state_in;
+    sk_sync_state* state_out;
+    int32_t do_clear;
+    int32_t buf_begin[SK_MAX_SAMPLES], buf_end[SK_MAX_SAMPLES];
+    sk_sync_region* regions;
+    int64_t region_cap;
+    int32_t* n_regions;
+    unsigned* err;
+};
+
+// SampleActiveRegionDetector::getPloidy(pos) (:280-284) over the sorted marks of one sample
+__device__ __forceinline__ int32_t ar_ploidy_at(const sk_ploidy_mark* marks, int32_t lo, int32_t hi, const int32_t default_ploidy, const int32_t pos)
+{
+    while (lo < hi) {
+        const int32_t mid = lo + (hi - lo) / 2;
+        const int32_t p = marks[mid].pos;
+        if (p == pos) return marks[mid].ploidy;
+        if (p < pos) lo = mid + 1;
+        else hi = mid;
+    }
+    return default_ploidy;
+}
+
+// AR3: one workgroup, AR2's shape.  Every wave turns 64 positions' flags into mask words in LDS -- a candidate word and a depth-zero word per
+// sample and one anchor word, the samples' finders being one -- 4 096 positions a turn; then one lane walks the words for all samples at once.
+// A sample's detector reads nothing of the others, and the synchroniser only reads the samples' start positions, so between two positions at
+// which some sample's coordinates change the close test (:137-153) gives one answer: the lane visits those positions only and closes the region
+// at the first call >= end + 9 since the last visit whose test passes.  While no synchronised region is open nobody reads the start positions
+// and AR2's shortcut holds per sample (a plain anchor only moves the start and the previous anchor); while one is open every anchor is visited.
+__global__ __launch_bounds__(AR_WALK_THREADS) void ar_sync_walk_kernel(const SyncArgs a)
+{
+    __shared__ u64 cand_w[SK_MAX_SAMPLES][AR_SYNC_WORDS], zero_w[SK_MAX_SAMPLES][AR_SYNC_WORDS], anchor_w[AR_SYNC_WORDS];
+    __shared__ sk_sync_state s_in, s;
+    __shared__ int bad_marks, failed;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int S = a.n_samples;
+    if (tid == 0) bad_marks = 0;
+    for (int k = tid; k < int(sizeof(sk_sync_state) / 4); k += AR_WALK_THREADS) { // (state_out may be state_in: read whole before anything is written)
+        const int32_t v = reinterpret_cast<const int32_t*>(a.state_in)[k];
+        reinterpret_cast<int32_t*>(&s_in)[k] = v;
+        reinterpret_cast<int32_t*>(&s)[k] = v;
+    }
+    __syncthreads();
+    // the marks: ascending positions per sample, ploidy 1 or 2 (the host entry refuses others with a message)
+    for (int smp = 0; smp < S; ++smp) {
+        const int32_t lo = a.mark_off[smp], hi = a.mark_off[smp + 1];
+        if (tid == 0 && (lo < 0 || hi < lo)) bad_marks = 1;
+        for (int64_t k = int64_t(lo) + tid; k < hi; k += AR_WALK_THREADS) {
+            const sk_ploidy_mark m = a.marks[k];
+            if ((m.ploidy != 1 && m.ploidy != 2) || (k + 1 < hi && !(m.pos < a.marks[k + 1].pos))) bad_marks = 1;
+        }
+    }
+    if (tid == 0 && a.default_ploidy != 1 && a.default_ploidy != 2) bad_marks = 1;
+    __syncthreads();
+
+    // the walking lane's own: the synchronised region, the first call whose close test has not been answered yet
+    int64_t n_out = 0, t_from = int64_t(a.win_begin) + 1;
+    bool bad = bad_marks != 0;
+
+    // no sample's unclosed start lies inside the region (:141-149)
+    const auto can_close = [&]() {
+        for (int smp = 0; smp < S; ++smp) {
+            const int32_t start = s.sample[smp].active_region_start_pos;
+            if (start >= 0 && start < s.sync_end - 1) return false;
+        }
+        return true;
+    };
+    // closeActiveRegion (:203-250) for the call closed_at
+    const auto close_region = [&](const int32_t closed_at) {
+        if (!(int64_t(s.sync_end) - s.sync_begin > 0)) { // :206
+            bad = true;
+            return;
+        }
+        if (n_out < a.region_cap) {
+            sk_sync_region* r = a.regions + n_out;
+            const int32_t begin = s.sync_begin, end = s.sync_end;
+            r->begin = begin;
+            r->end = end;
+            r->closed_at = closed_at;
+            r->prev_end = s.prev_end;
+            for (int smp = 0; smp < SK_MAX_SAMPLES; ++smp) r->ploidy[smp] = 0;
+            for (int smp = 0; smp < S; ++smp) {
+                const int32_t lo = a.mark_off[smp], hi = a.mark_off[smp + 1];
+                const int32_t left = ar_ploidy_at(a.marks, lo, hi, a.default_ploidy, begin), right = ar_ploidy_at(a.marks, lo, hi, a.default_ploidy, end - 1);
+                r->ploidy[smp] = uint8_t(left > right ? left : right); // :286-293
+            }
+            r->sample_mask = s.sample_mask;
+            r->pad = 0;
+        } else {
+            bad = true; // (the host entry refuses a cap below the bound)
+        }
+        ++n_out;
+        s.prev_end = s.sync_end;         // :248
+        s.sync_begin = s.sync_end = 0;   // :249
+        s.sample_mask = 0;
+    };
+    // processExistingActiveRegion (:133-154) for every call from t_from through upto, between which no sample's coordinates change
+    const auto close_through = [&](const int64_t upto) {
+        if (s.sync_end == 0 || !can_close()) return;
+        const int64_t first = int64_t(s.sync_end) + AR_SYNC_PADDING;
+        const int64_t at = first > t_from ? first : t_from;
+        if (at <= upto) close_region(int32_t(at));
+    };
+    // updateActiveRegionRange (:119-131)
+    const auto merge = [&](const int32_t begin, const int32_t end, const int smp) {
+        if (s.sync_end) {
+            if (begin < s.sync_begin) s.sync_begin = begin;
+            if (end > s.sync_end) s.sync_end = end;
+        } else {
+            s.sync_begin = begin;
+            s.sync_end = end;
+        }
+        s.sample_mask |= 1u << smp;
+    };
+
+    if (tid == 0 && !bad && a.n_pos > 0) {
+        close_through(t_from); // the first call's test reads the starts as they came in, before :341-347
+        t_from += 1;
+        for (int smp = 0; smp < S; ++smp) {
+            sk_ar_state& d = s.sample[smp];
+            if (d.is_beginning) { // :341-347, at the first call, pos = win_begin + 1
+                d.active_region_start_pos = d.anchor_pos_following_prev_variant = d.prev_anchor_pos = a.win_begin + 1;
+                d.is_beginning = 0;
+            }
+        }
+    }
+    for (int64_t c0 = 0; c0 < a.n_pos; c0 += AR_SYNC_CHUNK) {
+        const int n_here = int(min(int64_t(AR_SYNC_CHUNK), int64_t(a.n_pos) - c0));
+        const int words = (n_here + 63) / 64;
+        for (int item = wave; item < (S + 1) * words; item += AR_WALK_WAVES) { // (the same for a whole wave)
+            const int smp = item / words, w = item - smp * words;
+            const int64_t i = c0 + 64 * int64_t(w) + lane;
+            if (smp < S) {
+                bool c = false, z = false;
+                if (i < a.n_pos) {
+                    const int64_t at = int64_t(smp) * a.n_pos + i;
+                    c = a.is_candidate[at] != 0;
+                    z = a.sites[at].depth == 0u;
+                }
+                const u64 cw = __ballot(c), zw = __ballot(z);
+                if (lane == 0) {
+                    cand_w[smp][w] = cw;
+                    zero_w[smp][w] = zw;
+                }
+            } else {
+                const u64 aw = __ballot(i < a.n_pos && a.is_anchor[i] != 0);
+                if (lane == 0) anchor_w[w] = aw;
+            }
+        }
+        __syncthreads();
+        if (tid == 0 && !bad) {
+            for (int w = 0; w < words && !bad; ++w) {
+                const u64 A = anchor_w[w];
+                u64 any_c = 0;
+                for (int smp = 0; smp < S; ++smp) any_c |= cand_w[smp][w];
+                const int32_t base = int32_t(int64_t(a.win_begin) + c0 + 64 * int64_t(w));
+                u64 pending = ~0ull;
+                while (pending && !bad) {
+                    // the positions to visit: with a region open every event of any sample; otherwise per sample what AR2 visits
+                    u64 visit = 0, jumping = 0;
+                    if (s.sync_end != 0) {
+                        visit = any_c | A;
+                    } else {
+                        for (int smp = 0; smp < S; ++smp) {
+                            const sk_ar_state& d = s.sample[smp];
+                            const u64 C = cand_w[smp][w];
+                            if (d.num_variants == 0u && d.anchor_pos_following_prev_variant >= 0) {
+                                visit |= C & ~zero_w[smp][w];
+                                jumping |= 1ull << smp;
+                            } else {
+                                visit |= C | A;
+                            }
+                        }
+                    }
+                    visit &= pending;
+                    // the plain anchors before it: the last one counts (:385-395), for the samples that skip them
+                    const u64 before = visit ? ((visit & (~visit + 1ull)) - 1ull) : ~0ull;
+                    const u64 plain = A & pending & before;
+                    if (plain && jumping) {
+                        const int32_t at = base + (63 - __clzll(plain));
+                        for (int smp = 0; smp < S; ++smp)
+                            if ((jumping >> smp) & 1ull) s.sample[smp].active_region_start_pos = s.sample[smp].prev_anchor_pos = at;
+                    }
+                    if (!visit) break;
+                    const int bit = __ffsll(visit) - 1;
+                    const int32_t x = base + bit;
+                    close_through(int64_t(x) + 1); // the calls up to this one: the test comes before the samples' steps (:80)
+                    const bool ring = (A >> bit) & 1ull;
+                    for (int smp = 0; smp < S && !bad; ++smp) {
+                        const bool c = (cand_w[smp][w] >> bit) & 1ull;
+                        if (!c && !ring) continue; // (no event for this sample, :364)
+                        sk_ar_state d = s.sample[smp];
+                        bool made = false;
+                        sk_active_region region = {};
+                        if (!ar_step(d, x, c, (zero_w[smp][w] >> bit) & 1ull, ring, made, region)) {
+                            bad = true;
+                            break;
+                        }
+                        s.sample[smp] = d;
+                        if (made) merge(region.begin, region.end, smp);
+                    }
+                    t_from = int64_t(x) + 2;
+                    pending = bit == 63 ? 0ull : (~0ull << (bit + 1));
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        if (!bad) close_through(int64_t(a.win_begin) + a.n_pos);
+        if (!bad && a.do_clear) { // clear() (:98-111) over closeActiveRegionDetector (:413-440)
+            for (int smp = 0; smp < S && !bad; ++smp) {
+                sk_ar_state& d = s.sample[smp];
+                if (d.is_beginning) continue;
+                if (d.num_variants >= uint32_t(AR_MIN_VARIANTS)) {
+                    const bool no_start = d.active_region_start_pos < 0, no_end = d.anchor_pos_following_prev_variant < 0;
+                    if (!no_start || !no_end || a.buf_begin[smp] < a.buf_end[smp]) {
+                        if (no_start) d.active_region_start_pos = a.buf_begin[smp];
+                        if (no_end) d.anchor_pos_following_prev_variant = a.buf_end[smp] - 1;
+                        if (!(d.active_region_start_pos < d.anchor_pos_following_prev_variant)) { // :318
+                            bad = true;
+                            break;
+                        }
+                        merge(d.active_region_start_pos, d.anchor_pos_following_prev_variant + 1, smp);
+                    }
+                }
+                d.prev_anchor_pos = d.active_region_start_pos = d.anchor_pos_following_prev_variant = d.prev_variant_pos = -1; // clearCoordinates, is_beginning as it was
+                d.num_variants = 0;
+            }
+            if (!bad && s.sync_end) close_region(SK_SYNC_CLOSED_AT_CLEAR);
+        }
+        if (bad) atomicOr(a.err, unsigned(SK_DEVERR_SYNC_REGIONS));
+        *a.n_regions = bad ? 0 : int32_t(n_out);
+        failed = bad ? 1 : 0;
+    }
+    __syncthreads();
+    const sk_sync_state& out = failed ? s_in : s;
+    for (int k = tid; k < int(sizeof(sk_sync_state) / 4); k += AR_WALK_THREADS) reinterpret_cast<int32_t*>(a.state_out)[k] = reinterpret_cast<const int32_t*>(&out)[k];
+}
+
+// AR3i: region_id of the window's positions from the closed regions (setPosToActiveRegionIdMap, :267-278): the last region of at most 250
+// positions that covers the position
+__global__ __launch_bounds__(AR_SYNC_ID_THREADS) void ar_sync_region_id_kernel(const int32_t win_begin, const int32_t n_pos, const sk_sync_region* regions, const int32_t* n_regions,
+                                                                               const int64_t region_cap, int32_t* region_id)
+{
+    const int64_t i = int64_t(blockIdx.x) * AR_SYNC_ID_THREADS + threadIdx.x;
+    if (i >= n_pos) return;
+    int64_t n = *n_regions;
+    if (n > region_cap) n = region_cap;
+    const int64_t p = int64_t(win_begin) + i;
+    int32_t id = -1;
+    for (int64_t r = n - 1; r >= 0; --r) {
+        const int32_t begin = regions[r].begin, end = regions[r].end;
+        if (p >= begin && p < end && int64_t(end) - begin <= SK_HAP_MAX_REF_SPAN) {
+            id = begin;
+            break;
+        }
+    }
+    region_id[i] = id;
+}
+
+// AR3p: one sample's sk_region_params and sk_active_region records from the synchronised list
+__global__ __launch_bounds__(256) void ar_sync_params_kernel(const sk_sync_region* sync, const int32_t* n_regions, const int64_t region_cap, const int32_t sample,
+                                                             const int32_t buf_begin, const int32_t buf_end_at_clear, sk_active_region* regions, sk_region_params* params)
+{
+    const int64_t r = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    int64_t n = *n_regions;
+    if (n > region_cap) n = region_cap;
+    if (r >= n) return;
+    const int32_t closed_at = sync[r].closed_at;
+    if (regions) {
+        sk_active_region out;
+        out.begin = sync[r].begin;
+        out.end = sync[r].end;
+        out.made_at = closed_at;
+        regions[r] = out;
+    }
+    sk_region_params p;
+    p.buf_begin = buf_begin;
+    p.buf_end = closed_at == SK_SYNC_CLOSED_AT_CLEAR ? buf_end_at_clear : closed_at;
+    p.ploidy = sync[r].ploidy[sample];
+    p.pad = 0;
+    params[r] = p;
+}
+
+const char* ar_sync_issue(const int32_t n_samples, const int32_t win_begin, const int32_t n_pos, const int32_t default_ploidy, const int64_t region_cap)
+{
+    if (n_samples < 1 || n_samples > SK_MAX_SAMPLES) return "n_samples outside 1..SK_MAX_SAMPLES";
+    if (n_pos < 0 || region_cap < 0) return "negative size";
+    if (win_begin < 0) return "win_begin below zero";
+    if (int64_t(win_begin) + n_pos + 1 > INT32_MAX) return "the window ends beyond int32";
+    if (default_ploidy != 1 && default_ploidy != 2) return "default_ploidy must be 1 or 2";
+    if (region_cap < int64_t(n_pos) + 1) return "region_cap is below sk_sync_regions_bound";
+    return nullptr;
+}
+
 // m of initRepeatSpan(init_pos) (:62-64)
 int32_t ar_min_pos(const int32_t init_pos, const int32_t ref_offset)
 {
@@ -440,6 +751,159 @@ int sk_active_regions(int32_t win_begin, int32_t n_pos, const sk_intake_site* si
     }
     *state_out = out;
     *n_regions = n;
+    return 0;
+}
+
+void sk_sync_state_initial(sk_sync_state* s)
+{
+    for (int k = 0; k < SK_MAX_SAMPLES; ++k) sk_ar_state_initial(&s->sample[k]);
+    s->sync_begin = s->sync_end = 0; // known_pos_range2::clear
+    s->prev_end = -1;                // ActiveRegionDetector.hh:117
+    s->sample_mask = 0;
+}
+
+int64_t sk_sync_regions_bound(int32_t n_pos)
+{
+    if (n_pos < 0) return -1;
+    return int64_t(n_pos) + 1; // one close per call at most (processExistingActiveRegion runs once in it), and one in clear()
+}
+
+int sk_sync_active_regions_dev(int32_t n_samples, int32_t win_begin, int32_t n_pos, const sk_intake_site* dev_sites, const uint8_t* dev_is_candidate,
+                               const uint8_t* dev_is_anchor, const int32_t* dev_mark_off, const sk_ploidy_mark* dev_marks, int32_t default_ploidy,
+                               const sk_sync_state* dev_state_in, sk_sync_state* dev_state_out, int32_t do_clear, const int32_t* buf_begin,
+                               const int32_t* buf_end, sk_sync_region* dev_regions, int64_t region_cap, int32_t* dev_n_regions, int32_t* dev_region_id,
+                               void* hip_stream)
+{
+    if (const char* why = ar_sync_issue(n_samples, win_begin, n_pos, default_ploidy, region_cap)) return sk_fail(std::string("sk_sync_active_regions_dev: ") + why);
+    if (!dev_mark_off || !dev_state_in || !dev_state_out || !dev_regions || !dev_n_regions || (n_pos > 0 && (!dev_sites || !dev_is_candidate || !dev_is_anchor)) ||
+        (do_clear && (!buf_begin || !buf_end)))
+        return sk_fail("sk_sync_active_regions_dev: null argument");
+    SK_REQUIRE_INIT();
+    skrt::wakeHint();
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    SyncArgs a = {};
+    a.n_samples = n_samples;
+    a.win_begin = win_begin;
+    a.n_pos = n_pos;
+    a.sites = dev_sites;
+    a.is_candidate = dev_is_candidate;
+    a.is_anchor = dev_is_anchor;
+    a.mark_off = dev_mark_off;
+    a.marks = dev_marks;
+    a.default_ploidy = default_ploidy;
+    a.state_in = dev_state_in;
+    a.state_out = dev_state_out;
+    a.do_clear = do_clear ? 1 : 0;
+    for (int s = 0; s < n_samples && do_clear; ++s) {
+        a.buf_begin[s] = buf_begin[s];
+        a.buf_end[s] = buf_end[s];
+    }
+    a.regions = dev_regions;
+    a.region_cap = region_cap;
+    a.n_regions = dev_n_regions;
+    a.err = sk_ctx().dev_error_flags;
+    SK_LAUNCH(ar_sync_walk_kernel, dim3(1), dim3(AR_WALK_THREADS), 0, st, a);
+    if (dev_region_id && n_pos > 0)
+        SK_LAUNCH(ar_sync_region_id_kernel, dim3(unsigned((n_pos + AR_SYNC_ID_THREADS - 1) / AR_SYNC_ID_THREADS)), dim3(AR_SYNC_ID_THREADS), 0, st, win_begin, n_pos, dev_regions,
+                  dev_n_regions, region_cap, dev_region_id);
+    SK_HIP(skrt::getLastError());
+    return 0;
+}
+
+int sk_sync_active_regions(int32_t n_samples, int32_t win_begin, int32_t n_pos, const sk_intake_site* sites, const uint8_t* is_candidate,
+                           const uint8_t* is_anchor, const int32_t* mark_off, const sk_ploidy_mark* marks, int32_t default_ploidy,
+                           const sk_sync_state* state_in, sk_sync_state* state_out, int32_t do_clear, const int32_t* buf_begin, const int32_t* buf_end,
+                           sk_sync_region* regions, int64_t region_cap, int32_t* n_regions, int32_t* region_id)
+{
+    if (const char* why = ar_sync_issue(n_samples, win_begin, n_pos, default_ploidy, region_cap)) return sk_fail(std::string("sk_sync_active_regions: ") + why);
+    if (!mark_off || !state_in || !state_out || !regions || !n_regions || (n_pos > 0 && (!sites || !is_candidate || !is_anchor)) || (do_clear && (!buf_begin || !buf_end)))
+        return sk_fail("sk_sync_active_regions: null argument");
+    if (mark_off[0] < 0) return sk_fail("sk_sync_active_regions: negative size (mark_off[0] below zero)");
+    for (int32_t s = 0; s < n_samples; ++s) {
+        if (mark_off[s + 1] < mark_off[s]) return sk_fail("sk_sync_active_regions: negative size (mark_off is not ascending)");
+        if (mark_off[s + 1] > mark_off[s] && !marks) return sk_fail("sk_sync_active_regions: null argument");
+        for (int32_t k = mark_off[s]; k < mark_off[s + 1]; ++k) {
+            if (marks[k].ploidy != 1 && marks[k].ploidy != 2)
+                return sk_fail("sk_sync_active_regions: sample " + std::to_string(s) + ": the mark at " + std::to_string(marks[k].pos) + " holds a ploidy other than 1 or 2");
+            if (k + 1 < mark_off[s + 1] && !(marks[k].pos < marks[k + 1].pos))
+                return sk_fail("sk_sync_active_regions: sample " + std::to_string(s) + ": the ploidy marks are not in ascending order of position");
+        }
+    }
+    SK_REQUIRE_INIT();
+    skrt::wakeHint();
+    SkContext& ctx = sk_ctx();
+    SK_HIP(skrt::setDevice(ctx.device));
+    hipStream_t st = ctx.stream;
+    const size_t np = size_t(n_pos), ns = size_t(n_samples), n_marks = size_t(mark_off[n_samples]);
+    const int64_t bound = sk_sync_regions_bound(n_pos);
+    struct { sk_intake_site* sites; uint8_t* cand; uint8_t* anchor; int32_t* mark_off; sk_ploidy_mark* marks; sk_sync_state* state_in; sk_sync_state* state_out;
+             sk_sync_region* regions; int32_t* n; int32_t* region_id; } d;
+    int rc = 0;
+    if (sk_carve(d, [&](SkArena& ar) {
+            return decltype(d){ ar.up(sites, ns * np, 2, st, rc), ar.up(is_candidate, ns * np, 16, st, rc), ar.up(is_anchor, np, 16, st, rc), ar.up(mark_off, ns + 1, 1, st, rc),
+                                ar.up(marks, n_marks, 2, st, rc), ar.up(state_in, 1, 0, st, rc), ar.take<sk_sync_state>(1), ar.take<sk_sync_region>(size_t(bound) + 1),
+                                ar.take<int32_t>(1), ar.take<int32_t>(np + 4) };
+        }) || rc)
+        return 1;
+    if (sk_sync_active_regions_dev(n_samples, win_begin, n_pos, d.sites, d.cand, d.anchor, d.mark_off, d.marks, default_ploidy, d.state_in, d.state_out, do_clear, buf_begin,
+                                   buf_end, d.regions, bound, d.n, region_id ? d.region_id : nullptr, st))
+        return 1;
+    sk_sync_state out;
+    int32_t n = 0;
+    SK_HIP(skrt::memcpyAsync(&out, d.state_out, sizeof(sk_sync_state), hipMemcpyDeviceToHost, st));
+    SK_HIP(skrt::memcpyAsync(&n, d.n, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    SK_HIP(skrt::streamSynchronize(st));
+    if (sk_check_device_errors()) return 1; // an assertion would have fired: nothing is emitted
+    if (n < 0 || n > bound) return sk_fail("sk_sync_active_regions: region count out of range");
+    if (n > 0) SK_HIP(skrt::memcpyAsync(regions, d.regions, sizeof(sk_sync_region) * size_t(n), hipMemcpyDeviceToHost, st));
+    if (region_id && n_pos > 0) SK_HIP(skrt::memcpyAsync(region_id, d.region_id, sizeof(int32_t) * np, hipMemcpyDeviceToHost, st));
+    SK_HIP(skrt::streamSynchronize(st));
+    *state_out = out;
+    *n_regions = n;
+    return 0;
+}
+
+int sk_sync_region_params_dev(const sk_sync_region* dev_sync_regions, const int32_t* dev_n_regions, int64_t region_cap, int32_t sample, int32_t buf_begin,
+                              int32_t buf_end_at_clear, sk_active_region* dev_regions, sk_region_params* dev_params, void* hip_stream)
+{
+    if (region_cap < 0) return sk_fail("sk_sync_region_params_dev: negative size");
+    if (region_cap > INT32_MAX) return sk_fail("sk_sync_region_params_dev: region_cap beyond int32");
+    if (sample < 0 || sample >= SK_MAX_SAMPLES) return sk_fail("sk_sync_region_params_dev: sample outside 0..SK_MAX_SAMPLES - 1");
+    if (!dev_n_regions || (region_cap > 0 && (!dev_sync_regions || !dev_params))) return sk_fail("sk_sync_region_params_dev: null argument");
+    SK_REQUIRE_INIT();
+    skrt::wakeHint();
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    if (region_cap > 0)
+        SK_LAUNCH(ar_sync_params_kernel, dim3(unsigned((region_cap + 255) / 256)), dim3(256), 0, st, dev_sync_regions, dev_n_regions, region_cap, sample, buf_begin, buf_end_at_clear,
+                  dev_regions, dev_params);
+    SK_HIP(skrt::getLastError());
+    return 0;
+}
+
+int sk_sync_region_params(const sk_sync_region* sync_regions, int32_t n_regions, int32_t sample, int32_t buf_begin, int32_t buf_end_at_clear,
+                          sk_active_region* regions, sk_region_params* params)
+{
+    if (n_regions < 0) return sk_fail("sk_sync_region_params: negative size");
+    if (sample < 0 || sample >= SK_MAX_SAMPLES) return sk_fail("sk_sync_region_params: sample outside 0..SK_MAX_SAMPLES - 1");
+    if (n_regions > 0 && (!sync_regions || !params)) return sk_fail("sk_sync_region_params: null argument");
+    SK_REQUIRE_INIT();
+    skrt::wakeHint();
+    SkContext& ctx = sk_ctx();
+    SK_HIP(skrt::setDevice(ctx.device));
+    hipStream_t st = ctx.stream;
+    const size_t ng = size_t(n_regions);
+    struct { sk_sync_region* sync; int32_t* n; sk_active_region* regions; sk_region_params* params; } d;
+    int rc = 0;
+    if (sk_carve(d, [&](SkArena& ar) {
+            return decltype(d){ ar.up(sync_regions, ng, 1, st, rc), ar.up(&n_regions, 1, 0, st, rc), ar.take<sk_active_region>(ng + 2), ar.take<sk_region_params>(ng + 1) };
+        }) || rc)
+        return 1;
+    if (sk_sync_region_params_dev(d.sync, d.n, n_regions, sample, buf_begin, buf_end_at_clear, d.regions, d.params, st)) return 1;
+    if (n_regions > 0) {
+        if (regions) SK_HIP(skrt::memcpyAsync(regions, d.regions, sizeof(sk_active_region) * ng, hipMemcpyDeviceToHost, st));
+        SK_HIP(skrt::memcpyAsync(params, d.params, sizeof(sk_region_params) * ng, hipMemcpyDeviceToHost, st));
+    }
+    SK_HIP(skrt::streamSynchronize(st));
     return 0;
 }
 

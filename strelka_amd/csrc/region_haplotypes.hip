@@ -67,6 +67,7 @@ struct HapArgs
     const sk_intake_obs* obs;
     uint32_t max_indel_size;
     int32_t buf_begin, buf_end, ploidy;
+    const sk_region_params* params; // per region instead of the three above; nullptr: the same for all
     const sk_active_region* regions;
     const int32_t* n_regions;
     int64_t region_cap;
@@ -420,8 +421,22 @@ __global__ __launch_bounds__(64) void hap_region_kernel(const HapArgs a)
             }
             continue;
         }
+        int32_t buf_begin = a.buf_begin, buf_end = a.buf_end, ploidy = a.ploidy;
+        if (a.params) {
+            const sk_region_params p = a.params[slot];
+            buf_begin = p.buf_begin;
+            buf_end = p.buf_end;
+            ploidy = p.ploidy;
+            if (ploidy != 1 && ploidy != 2) { // (the host entry refuses this)
+                if (lane == 0) {
+                    atomicOr(a.err, unsigned(SK_DEVERR_HAPLOTYPES));
+                    hp_write_rec(rec, SK_HAP_BYPASSED, 0, 0, 0);
+                }
+                continue;
+            }
+        }
         // processHaplotypes :45-56
-        if (begin < a.buf_begin || end > a.buf_end || int64_t(end) - begin > SK_HAP_MAX_REF_SPAN) {
+        if (begin < buf_begin || end > buf_end || int64_t(end) - begin > SK_HAP_MAX_REF_SPAN) {
             if (lane == 0) hp_write_rec(rec, SK_HAP_BYPASSED, 0, 0, 0);
             continue;
         }
@@ -566,7 +581,6 @@ __global__ __launch_bounds__(64) void hap_region_kernel(const HapArgs a)
             // selectHaplotypes :439-483 with selectOrDropHaplotypesWithSameCount :486-516
             int n_sel = 0, n_same = 0;
             bool is_reference_selected = false;
-            const int ploidy = a.ploidy;
             auto select_or_drop = [&]() {
                 if (n_same > 0) {
                     const int after = n_sel + n_same;
@@ -764,28 +778,29 @@ size_t sk_region_haplotypes_scratch_bytes(int32_t n_reads, int64_t region_cap, i
     return hap_scratch_layout(n_reads, region_cap, seq_cap, support_cap).total;
 }
 
-int sk_region_haplotypes_dev(const char* dev_ref_seq, int32_t ref_offset, int32_t ref_len, int32_t n_reads, const int64_t* dev_read_off,
+// sk_region_haplotypes_dev and sk_region_haplotypes_params_dev: dev_params == nullptr takes (buf_begin, buf_end, ploidy) for every region
+static int hap_enqueue(const std::string& who, const char* dev_ref_seq, int32_t ref_offset, int32_t ref_len, int32_t n_reads, const int64_t* dev_read_off,
                              const uint8_t* dev_read_code, const int64_t* dev_path_off, const int32_t* dev_n_seg, const sk_path_seg* dev_path,
                              const int32_t* dev_pos, const uint8_t* dev_low_mapq, const uint8_t* dev_is_fwd_strand, const int64_t* dev_obs_off,
-                             const sk_intake_obs* dev_obs, uint32_t max_indel_size, int32_t buf_begin, int32_t buf_end, int32_t ploidy,
+                             const sk_intake_obs* dev_obs, uint32_t max_indel_size, int32_t buf_begin, int32_t buf_end, int32_t ploidy, const sk_region_params* dev_params,
                              const sk_active_region* dev_regions, const int32_t* dev_n_regions, int64_t region_cap, sk_region_haplotypes_rec* dev_recs,
                              uint8_t* dev_seq_pool, int64_t seq_cap, int32_t* dev_support_pool, int64_t support_cap, int64_t* dev_query_off,
                              int64_t* dev_totals, void* dev_scratch, size_t scratch_bytes, void* hip_stream)
 {
-    if (n_reads < 0 || ref_len < 0 || region_cap < 0 || seq_cap < 0 || support_cap < 0) return sk_fail("sk_region_haplotypes_dev: negative size");
-    if (region_cap > INT32_MAX) return sk_fail("sk_region_haplotypes_dev: region_cap beyond int32");
-    if (ploidy != 1 && ploidy != 2) return sk_fail("sk_region_haplotypes_dev: ploidy must be 1 or 2");
-    if (seq_cap < sk_region_haplotypes_seq_bound(region_cap)) return sk_fail("sk_region_haplotypes_dev: seq_cap is below sk_region_haplotypes_seq_bound");
+    if (n_reads < 0 || ref_len < 0 || region_cap < 0 || seq_cap < 0 || support_cap < 0) return sk_fail(who + ": negative size");
+    if (region_cap > INT32_MAX) return sk_fail(who + ": region_cap beyond int32");
+    if (!dev_params && ploidy != 1 && ploidy != 2) return sk_fail(who + ": ploidy must be 1 or 2");
+    if (seq_cap < sk_region_haplotypes_seq_bound(region_cap)) return sk_fail(who + ": seq_cap is below sk_region_haplotypes_seq_bound");
     if (support_cap < sk_region_haplotypes_support_bound(n_reads, region_cap))
-        return sk_fail("sk_region_haplotypes_dev: support_cap is below sk_region_haplotypes_support_bound");
-    if (!dev_n_regions || !dev_query_off || !dev_totals || (ref_len > 0 && !dev_ref_seq)) return sk_fail("sk_region_haplotypes_dev: null argument");
-    if (region_cap > 0 && (!dev_regions || !dev_recs)) return sk_fail("sk_region_haplotypes_dev: null argument");
-    if ((seq_cap > 0 && !dev_seq_pool) || (support_cap > 0 && !dev_support_pool)) return sk_fail("sk_region_haplotypes_dev: null argument");
+        return sk_fail(who + ": support_cap is below sk_region_haplotypes_support_bound");
+    if (!dev_n_regions || !dev_query_off || !dev_totals || (ref_len > 0 && !dev_ref_seq)) return sk_fail(who + ": null argument");
+    if (region_cap > 0 && (!dev_regions || !dev_recs)) return sk_fail(who + ": null argument");
+    if ((seq_cap > 0 && !dev_seq_pool) || (support_cap > 0 && !dev_support_pool)) return sk_fail(who + ": null argument");
     if (n_reads > 0 && (!dev_read_off || !dev_read_code || !dev_path_off || !dev_n_seg || !dev_path || !dev_pos || !dev_low_mapq || !dev_is_fwd_strand || !dev_obs_off))
-        return sk_fail("sk_region_haplotypes_dev: null argument");
+        return sk_fail(who + ": null argument");
     if (!dev_scratch || scratch_bytes < sk_region_haplotypes_scratch_bytes(n_reads, region_cap, seq_cap, support_cap))
-        return sk_fail("sk_region_haplotypes_dev: scratch is below sk_region_haplotypes_scratch_bytes");
-    if (reinterpret_cast<uintptr_t>(dev_scratch) & 15u) return sk_fail("sk_region_haplotypes_dev: scratch must be 16-byte aligned");
+        return sk_fail(who + ": scratch is below sk_region_haplotypes_scratch_bytes");
+    if (reinterpret_cast<uintptr_t>(dev_scratch) & 15u) return sk_fail(who + ": scratch must be 16-byte aligned");
     SK_REQUIRE_INIT();
     skrt::wakeHint();
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
@@ -811,6 +826,7 @@ int sk_region_haplotypes_dev(const char* dev_ref_seq, int32_t ref_offset, int32_
     a.buf_begin = buf_begin;
     a.buf_end = buf_end;
     a.ploidy = ploidy;
+    a.params = dev_params;
     a.regions = dev_regions;
     a.n_regions = dev_n_regions;
     a.region_cap = region_cap;
@@ -839,23 +855,53 @@ int sk_region_haplotypes_dev(const char* dev_ref_seq, int32_t ref_offset, int32_
     return 0;
 }
 
-int sk_region_haplotypes(const char* ref_seq, int32_t ref_offset, int32_t ref_len, int32_t n_reads, const int64_t* read_off, const uint8_t* read_code,
+int sk_region_haplotypes_dev(const char* dev_ref_seq, int32_t ref_offset, int32_t ref_len, int32_t n_reads, const int64_t* dev_read_off,
+                             const uint8_t* dev_read_code, const int64_t* dev_path_off, const int32_t* dev_n_seg, const sk_path_seg* dev_path,
+                             const int32_t* dev_pos, const uint8_t* dev_low_mapq, const uint8_t* dev_is_fwd_strand, const int64_t* dev_obs_off,
+                             const sk_intake_obs* dev_obs, uint32_t max_indel_size, int32_t buf_begin, int32_t buf_end, int32_t ploidy,
+                             const sk_active_region* dev_regions, const int32_t* dev_n_regions, int64_t region_cap, sk_region_haplotypes_rec* dev_recs,
+                             uint8_t* dev_seq_pool, int64_t seq_cap, int32_t* dev_support_pool, int64_t support_cap, int64_t* dev_query_off,
+                             int64_t* dev_totals, void* dev_scratch, size_t scratch_bytes, void* hip_stream)
+{
+    return hap_enqueue("sk_region_haplotypes_dev", dev_ref_seq, ref_offset, ref_len, n_reads, dev_read_off, dev_read_code, dev_path_off, dev_n_seg, dev_path, dev_pos, dev_low_mapq, dev_is_fwd_strand,
+                       dev_obs_off, dev_obs, max_indel_size, buf_begin, buf_end, ploidy, nullptr, dev_regions, dev_n_regions, region_cap, dev_recs, dev_seq_pool, seq_cap, dev_support_pool,
+                       support_cap, dev_query_off, dev_totals, dev_scratch, scratch_bytes, hip_stream);
+}
+
+int sk_region_haplotypes_params_dev(const char* dev_ref_seq, int32_t ref_offset, int32_t ref_len, int32_t n_reads, const int64_t* dev_read_off,
+                                    const uint8_t* dev_read_code, const int64_t* dev_path_off, const int32_t* dev_n_seg, const sk_path_seg* dev_path,
+                                    const int32_t* dev_pos, const uint8_t* dev_low_mapq, const uint8_t* dev_is_fwd_strand, const int64_t* dev_obs_off,
+                                    const sk_intake_obs* dev_obs, uint32_t max_indel_size, const sk_region_params* dev_params,
+                                    const sk_active_region* dev_regions, const int32_t* dev_n_regions, int64_t region_cap, sk_region_haplotypes_rec* dev_recs,
+                                    uint8_t* dev_seq_pool, int64_t seq_cap, int32_t* dev_support_pool, int64_t support_cap, int64_t* dev_query_off,
+                                    int64_t* dev_totals, void* dev_scratch, size_t scratch_bytes, void* hip_stream)
+{
+    if (!dev_params) return sk_fail("sk_region_haplotypes_params_dev: null argument");
+    return hap_enqueue("sk_region_haplotypes_params_dev", dev_ref_seq, ref_offset, ref_len, n_reads, dev_read_off, dev_read_code, dev_path_off, dev_n_seg, dev_path, dev_pos, dev_low_mapq, dev_is_fwd_strand,
+                       dev_obs_off, dev_obs, max_indel_size, 0, 0, 0, dev_params, dev_regions, dev_n_regions, region_cap, dev_recs, dev_seq_pool, seq_cap, dev_support_pool,
+                       support_cap, dev_query_off, dev_totals, dev_scratch, scratch_bytes, hip_stream);
+}
+
+// sk_region_haplotypes and sk_region_haplotypes_params: params == nullptr takes (buf_begin, buf_end, ploidy) for every region
+static int hap_host(const std::string& who, const char* ref_seq, int32_t ref_offset, int32_t ref_len, int32_t n_reads, const int64_t* read_off, const uint8_t* read_code,
                          const int64_t* path_off, const int32_t* n_seg, const sk_path_seg* path, const int32_t* pos, const uint8_t* low_mapq,
                          const uint8_t* is_fwd_strand, const int64_t* obs_off, const sk_intake_obs* obs, uint32_t max_indel_size, int32_t buf_begin,
-                         int32_t buf_end, int32_t ploidy, const sk_active_region* regions, int32_t n_regions, sk_region_haplotypes_rec* recs,
+                         int32_t buf_end, int32_t ploidy, const sk_region_params* params, const sk_active_region* regions, int32_t n_regions, sk_region_haplotypes_rec* recs,
                          uint8_t* seq_pool, int64_t seq_cap, int32_t* support_pool, int64_t support_cap, int64_t* query_off, int64_t* totals)
 {
-    if (n_reads < 0 || ref_len < 0 || n_regions < 0 || seq_cap < 0 || support_cap < 0) return sk_fail("sk_region_haplotypes: negative size");
-    if (ploidy != 1 && ploidy != 2) return sk_fail("sk_region_haplotypes: ploidy must be 1 or 2");
-    if (!query_off || !totals || (ref_len > 0 && !ref_seq) || (n_regions > 0 && (!regions || !recs))) return sk_fail("sk_region_haplotypes: null argument");
+    if (n_reads < 0 || ref_len < 0 || n_regions < 0 || seq_cap < 0 || support_cap < 0) return sk_fail(who + ": negative size");
+    if (!params && ploidy != 1 && ploidy != 2) return sk_fail(who + ": ploidy must be 1 or 2");
+    for (int32_t i = 0; params && i < n_regions; ++i)
+        if (params[i].ploidy != 1 && params[i].ploidy != 2) return sk_fail(who + ": region " + std::to_string(i) + ": ploidy must be 1 or 2");
+    if (!query_off || !totals || (ref_len > 0 && !ref_seq) || (n_regions > 0 && (!regions || !recs))) return sk_fail(who + ": null argument");
     if (n_reads > 0 && (!read_off || !read_code || !path_off || !n_seg || !path || !pos || !low_mapq || !is_fwd_strand || !obs_off))
-        return sk_fail("sk_region_haplotypes: null argument");
+        return sk_fail(who + ": null argument");
     int64_t n_bases = 0, n_segs = 0, n_obs = 0;
     if (n_reads > 0) {
-        if (read_off[0] < 0 || path_off[0] < 0 || obs_off[0] < 0) return sk_fail("sk_region_haplotypes: negative size (an offset below zero)");
+        if (read_off[0] < 0 || path_off[0] < 0 || obs_off[0] < 0) return sk_fail(who + ": negative size (an offset below zero)");
         for (int32_t r = 0; r < n_reads; ++r) {
             const int64_t len = read_off[r + 1] - read_off[r], slots = path_off[r + 1] - path_off[r];
-            const std::string where = "sk_region_haplotypes: read " + std::to_string(r) + ": ";
+            const std::string where = who + ": read " + std::to_string(r) + ": ";
             if (len < 0 || slots < 0 || obs_off[r + 1] < obs_off[r]) return sk_fail(where + "negative size (offsets are not ascending)");
             if (len > SK_PILEUP_MAX_READ_LEN) return sk_fail(where + "longer than SK_PILEUP_MAX_READ_LEN");
             if (n_seg[r] < 0 || int64_t(n_seg[r]) > slots) return sk_fail(where + "n_seg beyond the read's path slots");
@@ -865,13 +911,13 @@ int sk_region_haplotypes(const char* ref_seq, int32_t ref_offset, int32_t ref_le
         n_segs = path_off[n_reads];
         n_obs = obs_off[n_reads];
     }
-    if (n_obs > 0 && !obs) return sk_fail("sk_region_haplotypes: null argument");
+    if (n_obs > 0 && !obs) return sk_fail(who + ": null argument");
     for (int32_t i = 0; i < n_regions; ++i)
-        if (regions[i].end <= regions[i].begin) return sk_fail("sk_region_haplotypes: region " + std::to_string(i) + " is empty (end <= begin)");
+        if (regions[i].end <= regions[i].begin) return sk_fail(who + ": region " + std::to_string(i) + " is empty (end <= begin)");
     const int64_t seq_bound = sk_region_haplotypes_seq_bound(n_regions), support_bound = sk_region_haplotypes_support_bound(n_reads, n_regions);
-    if (seq_cap < seq_bound) return sk_fail("sk_region_haplotypes: seq_cap is below sk_region_haplotypes_seq_bound");
-    if (support_cap < support_bound) return sk_fail("sk_region_haplotypes: support_cap is below sk_region_haplotypes_support_bound");
-    if ((seq_bound > 0 && !seq_pool) || (support_bound > 0 && !support_pool)) return sk_fail("sk_region_haplotypes: null argument");
+    if (seq_cap < seq_bound) return sk_fail(who + ": seq_cap is below sk_region_haplotypes_seq_bound");
+    if (support_cap < support_bound) return sk_fail(who + ": support_cap is below sk_region_haplotypes_support_bound");
+    if ((seq_bound > 0 && !seq_pool) || (support_bound > 0 && !support_pool)) return sk_fail(who + ": null argument");
     SK_REQUIRE_INIT();
     skrt::wakeHint();
     SkContext& ctx = sk_ctx();
@@ -883,7 +929,7 @@ int sk_region_haplotypes(const char* ref_seq, int32_t ref_offset, int32_t ref_le
     {
         char* ref; int64_t* read_off; uint8_t* code; int64_t* path_off; int32_t* n_seg; sk_path_seg* path; int32_t* pos; uint8_t* low; uint8_t* fwd;
         int64_t* obs_off; sk_intake_obs* obs; sk_active_region* regions; int32_t* n_regions; sk_region_haplotypes_rec* recs; uint8_t* seq; int32_t* support;
-        int64_t* query_off; char* scratch; int64_t* totals;
+        int64_t* query_off; char* scratch; int64_t* totals; sk_region_params* params;
     } d;
     int rc = 0;
     // (+ 16 bytes and the like: kernels read whole words past an array's end; every piece starts at a multiple of 256 bytes, which the
@@ -894,11 +940,12 @@ int sk_region_haplotypes(const char* ref_seq, int32_t ref_offset, int32_t ref_le
                                 ar.up(low_mapq, nr, 16, st, rc), ar.up(is_fwd_strand, nr, 16, st, rc), ar.up(obs_off, no, 1, st, rc),
                                 ar.up(obs, size_t(n_obs), 1, st, rc), ar.up(regions, ng, 2, st, rc), ar.up(&n_regions, 1, 0, st, rc),
                                 ar.take<sk_region_haplotypes_rec>(ng + 1), ar.take<uint8_t>(size_t(seq_bound) + 16), ar.take<int32_t>(size_t(support_bound) + 4),
-                                ar.take<int64_t>(size_t(SK_HAP_MAX_SELECTED) * ng + 1), ar.take<char>(scratch_bytes + 16), ar.take<int64_t>(3) };
+                                ar.take<int64_t>(size_t(SK_HAP_MAX_SELECTED) * ng + 1), ar.take<char>(scratch_bytes + 16), ar.take<int64_t>(3),
+                                ar.up(params, params ? ng : 0, 1, st, rc) };
         }) || rc)
         return 1;
-    if (sk_region_haplotypes_dev(d.ref, ref_offset, ref_len, n_reads, d.read_off, d.code, d.path_off, d.n_seg, d.path, d.pos, d.low, d.fwd, d.obs_off, d.obs,
-                                 max_indel_size, buf_begin, buf_end, ploidy, d.regions, d.n_regions, n_regions, d.recs, d.seq, seq_bound, d.support, support_bound,
+    if (hap_enqueue(who + "_dev", d.ref, ref_offset, ref_len, n_reads, d.read_off, d.code, d.path_off, d.n_seg, d.path, d.pos, d.low, d.fwd, d.obs_off, d.obs,
+                    max_indel_size, buf_begin, buf_end, ploidy, params ? d.params : nullptr, d.regions, d.n_regions, n_regions, d.recs, d.seq, seq_bound, d.support, support_bound,
                                  d.query_off, d.totals, d.scratch, scratch_bytes, st))
         return 1;
     int64_t t[3] = { 0, 0, 0 };
@@ -907,13 +954,34 @@ int sk_region_haplotypes(const char* ref_seq, int32_t ref_offset, int32_t ref_le
     SK_HIP(skrt::streamSynchronize(st));
     if (sk_check_device_errors()) return 1;
     if (t[0] < 0 || t[0] > int64_t(SK_HAP_MAX_SELECTED) * n_regions || t[1] < 0 || t[1] > seq_bound || t[2] < 0 || t[2] > support_bound)
-        return sk_fail("sk_region_haplotypes: totals out of range");
+        return sk_fail(who + ": totals out of range");
     SK_HIP(skrt::memcpyAsync(query_off, d.query_off, 8 * size_t(t[0] + 1), hipMemcpyDeviceToHost, st));
     if (t[1] > 0) SK_HIP(skrt::memcpyAsync(seq_pool, d.seq, size_t(t[1]), hipMemcpyDeviceToHost, st));
     if (t[2] > 0) SK_HIP(skrt::memcpyAsync(support_pool, d.support, 4 * size_t(t[2]), hipMemcpyDeviceToHost, st));
     SK_HIP(skrt::streamSynchronize(st));
     for (int q = 0; q < 3; ++q) totals[q] = t[q];
     return 0;
+}
+
+int sk_region_haplotypes(const char* ref_seq, int32_t ref_offset, int32_t ref_len, int32_t n_reads, const int64_t* read_off, const uint8_t* read_code,
+                         const int64_t* path_off, const int32_t* n_seg, const sk_path_seg* path, const int32_t* pos, const uint8_t* low_mapq,
+                         const uint8_t* is_fwd_strand, const int64_t* obs_off, const sk_intake_obs* obs, uint32_t max_indel_size, int32_t buf_begin,
+                         int32_t buf_end, int32_t ploidy, const sk_active_region* regions, int32_t n_regions, sk_region_haplotypes_rec* recs,
+                         uint8_t* seq_pool, int64_t seq_cap, int32_t* support_pool, int64_t support_cap, int64_t* query_off, int64_t* totals)
+{
+    return hap_host("sk_region_haplotypes", ref_seq, ref_offset, ref_len, n_reads, read_off, read_code, path_off, n_seg, path, pos, low_mapq, is_fwd_strand, obs_off, obs, max_indel_size,
+                    buf_begin, buf_end, ploidy, nullptr, regions, n_regions, recs, seq_pool, seq_cap, support_pool, support_cap, query_off, totals);
+}
+
+int sk_region_haplotypes_params(const char* ref_seq, int32_t ref_offset, int32_t ref_len, int32_t n_reads, const int64_t* read_off, const uint8_t* read_code,
+                                const int64_t* path_off, const int32_t* n_seg, const sk_path_seg* path, const int32_t* pos, const uint8_t* low_mapq,
+                                const uint8_t* is_fwd_strand, const int64_t* obs_off, const sk_intake_obs* obs, uint32_t max_indel_size,
+                                const sk_region_params* params, const sk_active_region* regions, int32_t n_regions, sk_region_haplotypes_rec* recs,
+                                uint8_t* seq_pool, int64_t seq_cap, int32_t* support_pool, int64_t support_cap, int64_t* query_off, int64_t* totals)
+{
+    if (!params) return sk_fail("sk_region_haplotypes_params: null argument");
+    return hap_host("sk_region_haplotypes_params", ref_seq, ref_offset, ref_len, n_reads, read_off, read_code, path_off, n_seg, path, pos, low_mapq, is_fwd_strand, obs_off, obs, max_indel_size,
+                    0, 0, 0, params, regions, n_regions, recs, seq_pool, seq_cap, support_pool, support_cap, query_off, totals);
 }
 
 } // extern "C"

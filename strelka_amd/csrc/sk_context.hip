@@ -389,9 +389,11 @@ int sk_check_device_errors(void)
     if (flags & SK_DEVERR_ACTIVE_REGION)
         return sk_fail("sk_active_regions_dev: a region's start is not before its end anchor (createActiveRegion's assertion) or region_cap too small, or sk_ref_anchors_dev: a span_pos before the finder's first position");
     if (flags & SK_DEVERR_HAPLOTYPES)
-        return sk_fail("sk_region_haplotypes_dev: a read longer than SK_PILEUP_MAX_READ_LEN or with descending offsets, an empty region, or a pool too small");
+        return sk_fail("sk_region_haplotypes_dev: a read longer than SK_PILEUP_MAX_READ_LEN or with descending offsets, an empty region, a per-region ploidy other than 1 or 2, or a pool too small");
     if (flags & SK_DEVERR_ALLELES)
         return sk_fail("sk_region_alleles_dev: a haplotype record outside the sequence pool or with more than two alternates, a counted region of no or more than 250 positions, or a capacity below its bound");
+    if (flags & SK_DEVERR_SYNC_REGIONS)
+        return sk_fail("sk_sync_active_regions_dev: a region's start is not before its end anchor (createActiveRegion's assertion), a synchronised region of no positions (closeActiveRegion's assertion), ploidy marks not ascending or other than 1 or 2, or region_cap too small");
     return sk_fail("strelka_amd: a kernel reported an error");
 }
 
