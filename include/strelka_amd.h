@@ -128,6 +128,14 @@ int sk_debug_f5_tail_order(const int32_t* cal_off, int32_t n_reads, int32_t wave
 /** Test hook: how often the device read path's job runs of this process have launched that table kernel (a job that fits the grid, or
  *  one run with $SK_F5_TAIL_SHIFT=0, launches none). */
 int64_t sk_debug_f5_tail_launches(void);
+/** Test hook: over the device read path's job runs of this process, the rounds of 64 candidate alignments that the fused scoring
+ *  kernel's idle waves scored for a read owned by another wave of their block (0 throughout with $SK_F5_SHARE=0).  Whether a given
+ *  round is helped is a matter of timing; the scores do not depend on it. */
+int64_t sk_debug_f5_shared_rounds(void);
+/** Test hook: over the fused scoring kernel's launches by this process's job runs, the rounds AFTER a read's first in which a record
+ *  outside the kernel's compact form (more than 16 path segments or 8 indels, an index outside the table) left the job to the staged
+ *  kernels.  Tests look for such a job by it. */
+int64_t sk_debug_f5_late_turn_downs(void);
 
 /** Host copies of the q-score tables the kernels use (71 entries each, Q0..Q70; L/blt_util/qscore_cache.hh:66-68). */
 int sk_get_qscore_tables(double* q2p, double* q2lncompe, double* q2lne);

@@ -247,7 +247,7 @@ EXPORTS = [
     "sk_realign_options_default", "sk_realign_job_create", "sk_realign_job_destroy", "sk_realign_job_error",
     "sk_realign_job_set_reference", "sk_realign_job_set_indels", "sk_realign_job_add_read", "sk_realign_job_add_reads", "sk_realign_job_get_batch",
     "sk_realign_job_finish", "sk_realign_job_run", "sk_realign_job_n_reads", "sk_realign_job_read_result",
-    "sk_realign_job_clear_reads", "sk_realign_job_rescore", "sk_realign_job_indels_consulted", "sk_realign_job_enumeration_counts", "sk_realign_device_job_counts", "sk_debug_f5_tail_order", "sk_debug_f5_tail_launches", "sk_realign_reference_reads_outside", "sk_realign_job_stage3_counts", "sk_make_start_pos_alignment", "sk_get_end_pin_start_pos",
+    "sk_realign_job_clear_reads", "sk_realign_job_rescore", "sk_realign_job_indels_consulted", "sk_realign_job_enumeration_counts", "sk_realign_device_job_counts", "sk_debug_f5_tail_order", "sk_debug_f5_tail_launches", "sk_debug_f5_shared_rounds", "sk_debug_f5_late_turn_downs", "sk_realign_reference_reads_outside", "sk_realign_job_stage3_counts", "sk_make_start_pos_alignment", "sk_get_end_pin_start_pos",
     "sk_germline_options_default", "sk_dependent_eprob", "sk_dependent_eprob_dev", "sk_site_digt_call",
     "sk_site_digt_call_dev", "sk_site_digt_call_fused", "sk_site_digt_call_fused_dev",
     "sk_somatic_snv_options_default", "sk_somatic_snv_call_batch", "sk_somatic_snv_call_batch_dev",
@@ -305,6 +305,10 @@ def lib():
         L.sk_debug_f5_tail_order.argtypes = [c_void_p, C.c_int32, C.c_int32, C.c_int32, c_void_p, c_void_p, c_void_p]
         L.sk_debug_f5_tail_launches.argtypes = []
         L.sk_debug_f5_tail_launches.restype = C.c_int64
+        L.sk_debug_f5_shared_rounds.argtypes = []
+        L.sk_debug_f5_shared_rounds.restype = C.c_int64
+        L.sk_debug_f5_late_turn_downs.argtypes = []
+        L.sk_debug_f5_late_turn_downs.restype = C.c_int64
         L.sk_realign_reference_reads_outside.argtypes = []
         L.sk_realign_reference_reads_outside.restype = C.c_int64
         L.sk_realign_job_stage3_counts.argtypes = [c_void_p, c_void_p, c_void_p]
@@ -1069,6 +1073,16 @@ class RealignJob:
     def f5_tail_launches():
         """launches of the table kernel of F5's last hand-outs by this process's job runs (sk_debug_f5_tail_launches)"""
         return int(lib().sk_debug_f5_tail_launches())
+
+    @staticmethod
+    def f5_shared_rounds():
+        """rounds of F5 scored by a wave other than their read's owner, over this process's job runs (sk_debug_f5_shared_rounds)"""
+        return int(lib().sk_debug_f5_shared_rounds())
+
+    @staticmethod
+    def f5_late_turn_downs():
+        """rounds after a read's first in which F5 left the job to the staged kernels, over this process's job runs (sk_debug_f5_late_turn_downs)"""
+        return int(lib().sk_debug_f5_late_turn_downs())
 
     @staticmethod
     def f5_tail_order(cal_off, waves, shift):

@@ -318,7 +318,8 @@ enum { SEARCH_LEVELS = Caps::K + 2,       // level launches after which no searc
        CNT_UNHANDLED = Caps::K + 7,       // reads F5 turned down
        CNT_DYN = Caps::K + 8,             // [DYN_COUNT] the scans' results
        CNT_QUEUE = CNT_DYN + DYN_COUNT,   // [2] F5's read queue (FusedScoreArgs::queue)
-       N_COUNTERS = CNT_QUEUE + 2 };
+       CNT_SHARED = CNT_QUEUE + 2,        // F5's rounds scored by a wave other than their read's owner (FusedScoreArgs::shared_rounds)
+       N_COUNTERS = CNT_SHARED + 2 };     // ([CNT_SHARED + 1]: rounds after a read's first that turned the read down)
 static_assert(CNT_LEVELS + SEARCH_LEVELS + 1 == CNT_LEAVES && CNT_NODES > CNT_LEAVES && CNT_NODES + 2 <= CNT_UNHANDLED, "the counters' slots overlap");
 
 template <typename V> // (int; unsigned long long: two 32-bit counts scanned as one value, tail_order_kernel)
@@ -868,6 +869,10 @@ struct FusedScoreArgs
     // tail_order[h - tail_first], every other hand-out h is read h; tail_n = 0: the job's own order throughout
     const int32_t* tail_order;
     uint32_t tail_first, tail_n;
+    // round sharing (flatten_score_kernel): off with 0 ($SK_F5_SHARE); the rounds scored by a wave other than their read's owner
+    int32_t share;
+    unsigned* shared_rounds; // [2]: the helped rounds that were scored; the rounds after a read's first that turned their read down
+                             // (sk_debug_f5_late_turn_downs: what tests look for a case by)
 };
 
 // a candidate alignment's slot in LDS: the walk's output -- up to F5_SEGS + 1 transitions, one per op that covers read positions and
@@ -877,8 +882,9 @@ struct FusedScoreArgs
 // goes from 17.8 KB to under 10 KB and a CU holds 16 of them instead of 9 (profiles/r04_a5_history.txt: a wave alone on a CU takes as
 // long as nine sharing it; with sixteen the vector unit is ~85 % busy, profiles/r05_f5_history.txt).
 constexpr int F5_SEGS = 16, F5_INDELS = 8;
-constexpr int F5_STAMPS = 10; // $SK_F5_TIMING: a read's stamps (f5_read; the ninth is the cycles of the draw that handed it out, the
-                              // tenth the 100 MHz counter at the read's start: where the read lies in the launch)
+constexpr int F5_STAMPS = 11; // $SK_F5_TIMING: a read's stamps (f5_prologue, f5_round; the ninth is the cycles of the draw that handed
+                              // it out, the tenth the 100 MHz counter at the read's start: where the read lies in the launch, the
+                              // eleventh the rounds its owner scored itself)
 constexpr int F5_SLOT = (F5_SEGS + 1) | 1; // (odd stride: conflict-free)
 __device__ __forceinline__ int f5_ent_word(const int k) { return k; }
 // doubles per read position: agree, 0.0, differ -- the read's own cases folded in (a '=' base: differ = agree; an N base and the pad
@@ -909,9 +915,10 @@ struct F5Lds
 // (the CU hands LDS out in 1 280-byte pieces: 10 240 bytes are sixteen waves to a CU, one byte more fourteen; the 256-base form,
 // ~12.4 KB, still fits three four-wave blocks)
 constexpr int F5_Q_TERMS = 2 * (SK_NQ + 1); // the block's copy of q2lncompe and q2mis
+constexpr size_t F5_SHARE_BYTES = 36; // a wave's claim word and descriptor (F5Share), and 8 bytes a block for its count of busy waves
 constexpr size_t f5_block_granules(const size_t lds_object, const int waves) // a block's LDS in the CU's 1 280-byte pieces (128 to a CU)
 {
-    return (lds_object * size_t(waves) + 8 * size_t(F5_Q_TERMS) + 1279) / 1280;
+    return ((lds_object + F5_SHARE_BYTES) * size_t(waves) + 8 * size_t(F5_Q_TERMS) + 8 + 1279) / 1280;
 }
 static_assert(sizeof(F5Lds<152>) <= 10240 && 2 * f5_block_granules(sizeof(F5Lds<152>), 8) <= 128, "two eight-wave blocks of the short-read form to a CU");
 static_assert(3 * f5_block_granules(sizeof(F5Lds<F5_MAX_READ>), 4) <= 128, "three four-wave blocks of the long-read form to a CU");
@@ -1211,20 +1218,48 @@ constexpr int F5_INS_REG = 4;  // inserts of up to 64 bases each whose bytes the
 // later round waits for its records only (its list[] entry is asked for a round ahead).  The two terms of a quality come from the
 // block's copy in LDS (q_terms: q2lncompe, then q2mis).  Not built: the read's codes and qualities as words and S.read written with
 // word stores -- they are loaded and stored a byte a lane (up to three of each in flight at once, no wait between them).
+//
+// A read is scored in two parts.  f5_prologue is its owner's alone: everything up to the first round -- the loads above, the read, the
+// pool, the rows of terms, the order and (where the job's table fits it) the table copy written into the owner's LDS object, which
+// nothing writes again until the owner's next read.  f5_round is one round of up to 64 candidate alignments: staging, walk, sums, the
+// consulted marks, the scores' store.  It reads the read's data through a pointer and writes the EXECUTING wave's slots only, so that
+// a wave other than the owner can run it (flatten_score_kernel); what it needs of the read beyond the LDS object is in F5Desc.
+struct F5Desc // a read's uniforms, as a round needs them
+{
+    int32_t r, c0, ncr, L, P, win_begin, sorted_order;
+};
+// what the owner carries from the prologue into its rounds and from a round into its next one
+struct F5Own
+{
+    int32_t slot_next;      // where the lane's record of the owner's coming round is (list[] a round ahead)
+    F5Raw raw0;             // round 0's records, asked for in group 3
+    int my_ins_idx;         // lane k < n_ins: the read's insert k (a job whose table does not fit the copy places it per round)
+    int32_t my_ins_off;
+    unsigned long long stamp[F5_STAMPS], wall0; // $SK_F5_TIMING
+};
+// a wave's published read, in the block's LDS (flatten_score_kernel: round sharing)
+struct F5Share
+{
+    uint32_t claim; // the next round nobody has claimed | the read's rounds << 16; 0: nothing open
+    F5Desc d;
+    uint32_t dry_at; // the wave has drawn dry: the 100 MHz counter's low word then, | 1 (0: not yet)
+};
+static_assert(sizeof(F5Share) == F5_SHARE_BYTES, "f5_block_granules counts the claim words and descriptors");
+
 template <int MAXR, bool TIMING>
-__device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F5Lds<MAXR>& S, const double* const q_terms,
-                                        const unsigned long long draw_cycles)
+__device__ __forceinline__ bool f5_prologue(const FusedScoreArgs& fa, const int r, F5Lds<MAXR>& S, const double* const q_terms, F5Desc& desc,
+                                            F5Own& own) // false: the read has nothing to score here
 {
     auto now = [&]() -> unsigned long long { return TIMING ? (unsigned long long)clock64() : 0ull; };
     const FlatArgs& a = fa.f;
+    unsigned long long(&stamp)[F5_STAMPS] = own.stamp;
     // (the lane as a value of this read's: what is computed from it -- addresses of the loads below -- is computed here, not once
     // per kernel and kept in scratch memory, whose reload is one more wait in the middle of a group)
     int lane_of_read = threadIdx.x & 63;
     __asm__ volatile("" : "+v"(lane_of_read));
     const int lane = lane_of_read;
-    unsigned long long stamp[F5_STAMPS];
     stamp[0] = now(); // (before group 1: the prologue's figure holds every trip of the read but the draw, as it did)
-    const unsigned long long wall0 = TIMING ? (unsigned long long)wall_clock64() : 0ull; // (the constant 100 MHz counter: the block's life in time)
+    own.wall0 = TIMING ? (unsigned long long)wall_clock64() : 0ull; // (the constant 100 MHz counter: the block's life in time)
     // ---- group 1 (the empty statement keeps the loads together above the early return: every value is asked for before the first
     // is looked at; they are the same in every lane)
     int g1_c0 = a.cal_off[r], g1_c1 = a.cal_off[r + 1];
@@ -1243,14 +1278,13 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
     const int32_t win_begin = __builtin_amdgcn_readfirstlane(g1_win_begin);
     const int n_ins = __builtin_amdgcn_readfirstlane(g1_n_ins);
     const int32_t win_len = __builtin_amdgcn_readfirstlane(g1_win_len);
-    const double ln_quarter = fa.tab->ln_quarter, ln_noncand = fa.tab->ln_noncand;
     const int ncr = c1 - c0;
-    if (ncr == 0 || status_r != ST_OK) return;
+    if (ncr == 0 || status_r != ST_OK) return false;
     for (int i = 1; i < F5_STAMPS; ++i) stamp[i] = 0;
     const int32_t L = int32_t(ro1 - ro);
     if (L > MAXR || P > F5_MAX_POOL) {
         if (lane == 0) atomicAdd(fa.n_unhandled, 1);
-        return;
+        return false;
     }
     // the job's table fits the copy: one copy per read, every index relative to entry 0
     const int job_n_tab = a.job.n_tab;
@@ -1390,7 +1424,7 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
     }
     // (every lane loads -- one without an alignment the record its slot_next names, 0 or a former round's, which nothing looks at:
     // a load that some lanes skip is merged with the registers' former values, and that merge waits for the load where it is issued)
-    F5Raw raw0 = f5_load_raw(a.pool + slot_next);
+    own.raw0 = f5_load_raw(a.pool + slot_next);
     // ---- the pool's bytes (as pool_fill_kernel), the read, its rows of terms, the pool's layout
     if (a.ref_outside && lane == 0) { // (the window's positions that lie outside the job's reference segment: they read as N)
         const int64_t b = max(int64_t(win_begin), int64_t(a.ref_offset));
@@ -1454,18 +1488,57 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
             }
         }
     }
+    desc.r = r, desc.c0 = c0, desc.ncr = ncr, desc.L = L, desc.P = P, desc.win_begin = win_begin, desc.sorted_order = sorted_order ? 1 : 0;
+    own.slot_next = slot_next;
+    own.my_ins_idx = my_ins_idx;
+    own.my_ins_off = my_ins_off;
+    return true;
+}
 
-    for (int j0 = 0; j0 < ncr; j0 += 64) {
+// the place of alignment 64 j + lane of the read in list[] (a round's lanes take the read's alignments in the set's order, or after the
+// sort: the order's bytes lie past the pool's in the read's LDS object)
+template <typename LDS>
+__device__ __forceinline__ int f5_list_index(const LDS& D, const F5Desc& d, const int at)
+{
+    const uint8_t* const order = D.hap + ((d.P + 8 + 3) & ~3);
+    return d.c0 + (d.sorted_order ? int(order[at]) : at);
+}
+
+// One round: alignments [64 j, 64 j + 64) of the read d, whose data the prologue left in D.  `mine`: the executing wave is the read's
+// owner (D is its own LDS object); else it is a helper -- it reads D, writes its own slots (myslot), and has loaded own.slot_next at the
+// round's start.  The owner's round 0 finds its records asked for by the prologue; every other round asks for them here.  `next_j` (the
+// owner's): called between the walk and the sums, it names the owner's next round or -1, so that list[] of that round is asked for
+// behind the sums.  Returns false where the round ends the read for this form (a record beyond the compact form, an index outside the
+// table: counted in *n_unhandled, the staged chain takes the job).
+template <int MAXR, bool TIMING, typename NextRound>
+__device__ __forceinline__ bool f5_round(const FusedScoreArgs& fa, F5Lds<MAXR>& D, uint32_t* const slots, const F5Desc& d, const int j, const bool mine,
+                                         F5Own& own, NextRound next_j, int& j_next)
+{
+    auto now = [&]() -> unsigned long long { return TIMING ? (unsigned long long)clock64() : 0ull; };
+    const FlatArgs& a = fa.f;
+    unsigned long long(&stamp)[F5_STAMPS] = own.stamp; // (a helper's rounds are not stamped: the stamps are a read's, stored by its owner)
+    F5Lds<MAXR>& S = D;
+    F5Raw& raw0 = own.raw0;
+    int32_t& slot_next = own.slot_next;
+    const int lane = threadIdx.x & 63;
+    const int r = d.r, c0 = d.c0, ncr = d.ncr, job_n_tab = a.job.n_tab;
+    const int32_t L = d.L, P = d.P, win_begin = d.win_begin;
+    const int my_ins_idx = own.my_ins_idx;
+    const int32_t my_ins_off = own.my_ins_off;
+    const double ln_quarter = fa.tab->ln_quarter, ln_noncand = fa.tab->ln_noncand; // (asked for here, looked at by the sums)
+    {
+        const int j0 = 64 * j;
         const int nc = min(64, ncr - j0);
         f5_wave_sync(); // (pool and read complete; the previous round's slots read; the order written)
         const unsigned long long ta = now();
-        if (j0 == 0) stamp[1] = ta; // prologue done
+        if (mine && j0 == 0) stamp[1] = ta; // prologue done
         // ---- the round's records, a lane its own: header + F5_SEGS path segments (five 16-byte loads) + F5_INDELS indel indices, all in
         // flight at once; a record with more of either is left to the staged chain
         const bool has = lane < nc;
-        uint32_t* const myslot = S.slot + lane * F5_SLOT;
+        uint32_t* const myslot = slots + lane * F5_SLOT;
+        const bool whole_tab = job_n_tab <= F5_TAB; // (a helper's read is of such a job: only those are published)
         bool fits = true;
-        const int my_j = has ? (sorted_order ? int(order[j0 + lane]) : j0 + lane) : 0; // the lane's alignment among the read's
+        const int my_j = has ? f5_list_index(S, d, j0 + lane) - c0 : 0; // the lane's alignment among the read's
         F5Rec rec;
         rec.w0 = rec.w1 = rec.w2 = 0;
         rec.types = 0;
@@ -1473,7 +1546,7 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
         rec.ind = 0;
         rec.ind_lo = 0;
         uint64_t ind_raw0 = 0, ind_raw1 = 0; // the record's eight 16-bit indel indices, until the round's table copy is placed
-        if (j0 > 0) raw0 = f5_load_raw(a.pool + slot_next);
+        if (!mine || j0 > 0) raw0 = f5_load_raw(a.pool + slot_next);
         if (has) {
             const F5Raw w = raw0;
             const uint4 q0 = w.q0, q1 = w.q1, q2 = w.q2, q3 = w.q3, q4 = w.q4;
@@ -1514,8 +1587,11 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
             }
             // (a record beyond the compact form, an index that is none of the table's: the staged chain takes the job)
             if (__any((has && !fits) || out_of_table)) {
-                if (lane == 0) atomicAdd(fa.n_unhandled, 1);
-                return;
+                if (lane == 0) {
+                    atomicAdd(fa.n_unhandled, 1);
+                    if (j > 0) atomicAdd(fa.shared_rounds + 1, 1u); // (diagnostics: a round after the read's first turned it down)
+                }
+                return false;
             }
             uint64_t ind = 0;
 #pragma unroll
@@ -1542,8 +1618,11 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
             const int n_tab = (lo <= hi) ? hi - lo + 1 : 0;
             // (a record beyond the compact form, indices further apart than the copy holds: the staged chain takes the job)
             if (__any(has && !fits) || (n_tab > 0 && lo < 0) || n_tab > F5_TAB) {
-                if (lane == 0) atomicAdd(fa.n_unhandled, 1);
-                return;
+                if (lane == 0) {
+                    atomicAdd(fa.n_unhandled, 1);
+                    if (j > 0) atomicAdd(fa.shared_rounds + 1, 1u); // (diagnostics: a round after the read's first turned it down)
+                }
+                return false;
             }
             tab_lo = n_tab ? lo : 0;
             // (every index of the round's records lies in [tab_lo, tab_lo + n_tab), n_tab <= F5_TAB: 6 bits relative to tab_lo)
@@ -1600,7 +1679,9 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
             }
             (void)tA1;
         }
-        if (j0 + 64 + lane < ncr) slot_next = a.list[c0 + (sorted_order ? int(order[j0 + 64 + lane]) : j0 + 64 + lane)];
+        // (the owner's next round, named before the sums: its list[] entries travel while they run)
+        j_next = mine ? next_j() : -1;
+        if (j_next >= 0 && 64 * j_next + lane < ncr) slot_next = a.list[f5_list_index(S, d, 64 * j_next + lane)];
         __builtin_amdgcn_wave_barrier();
         const unsigned long long td = now();
         stamp[4] += td - tc; // phase A
@@ -1614,18 +1695,29 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
         raw0.q0 = raw0.q1 = raw0.q2 = raw0.q3 = raw0.q4 = make_uint4(0, 0, 0, 0);
         raw0.i0 = raw0.i1 = raw0.i2 = raw0.i3 = 0;
         stamp[5] += now() - td; // phase B
+        if (mine) stamp[10] += 1; // (rounds the owner scored itself)
     }
-    if (TIMING && fa.dbg && lane == 0) { // (the build without the stamps has no store of them either)
-        stamp[6] = now();
-        stamp[3] = TIMING ? (unsigned long long)wall_clock64() - wall0 : 0ull;
+    return true;
+}
+
+// $SK_F5_TIMING: the owner's last rounds are over -- the read's stamps go out (a round a helper still runs ends later: the stamps
+// are the owner's time on the read)
+template <bool TIMING>
+__device__ __forceinline__ void f5_store_stamps(const FusedScoreArgs& fa, const int r, F5Own& own, const unsigned long long draw_cycles)
+{
+    if (TIMING && fa.dbg && (threadIdx.x & 63) == 0) { // (the build without the stamps has no store of them either)
+        unsigned long long(&stamp)[F5_STAMPS] = own.stamp;
+        stamp[6] = (unsigned long long)clock64();
+        stamp[3] = (unsigned long long)wall_clock64() - own.wall0;
         stamp[8] = draw_cycles; // the draw that handed this read out, from before the atomic to its value in a scalar register (0: the
                                 // wave's first read, which is not drawn)
-        stamp[9] = wall0;
+        stamp[9] = own.wall0;
         for (int i = 0; i < F5_STAMPS; ++i) fa.dbg[size_t(r) * F5_STAMPS + i] = stamp[i];
     }
 }
 
-// A wave per read, WAVES waves to a block (each wave with an LDS object of its own; nothing is shared between them).  With a block per
+// A wave per read, WAVES waves to a block (each wave with an LDS object of its own, which it alone writes; at the launch's end a
+// block-mate may read it: ROUND SHARING below).  With a block per
 // read the kernel was bound by the rate at which the dispatcher places workgroups (65 536 one-wave blocks went out at ~30 per us, a block
 // lives ~58 us: ~7 of a CU's 16 slots filled); eight waves to a block: 2.23 -> 1.67 ms per 65 536 reads (profiles/r05_f5_history.txt).
 // The waves TAKE their reads from a queue (one counter, one atomic per read; a grid of the blocks the device holds at a time).  With read r
@@ -1641,35 +1733,160 @@ __device__ __forceinline__ void f5_read(const FusedScoreArgs& fa, const int r, F
 // (1.025 -> 0.981 ms, profiles/r09_f5_history.txt; a later draw costs a wave 3 700 - 4 600 cycles at this load, the `draw` figure of
 // $SK_F5_TIMING).  What is handed out is a number h; it names read h except among the launch's last hand-outs, whose reads are taken
 // from a table in which the reads of several rounds stand earlier than in the job (tail_order_kernel, below).  A wave whose number is
-// past the last read leaves without a draw.  The last wave to leave puts the queue back to zero -- every wave counts itself out after
+// past the last read makes no draw.  The last wave to leave puts the queue back to zero -- every wave counts itself out after
 // its last draw, whether it drew or not -- so that the next launch, the same buffers, the same stream, finds it as this one did.
+//
+// ROUND SHARING.  The launch used to end a heavy read's life after its last hand-out (~135 us of ~0.92 ms, profiles/r10_f5_history.txt): a
+// read of three or four rounds drawn late keeps one wave busy while its block-mates have left.  Now a wave that has drawn DRY does not
+// leave: it takes whole rounds of reads owned by waves of its own block.  The owner's prologue has left the read, the pool, the order, the
+// rows of terms and the table copy in its LDS object, which nothing writes again before the owner's next prologue; the helper reads them
+// where they lie and writes its own slots, so no second prologue runs and nothing but the round's own records is read from HBM.
+//   publication  A read of more than one round in a job whose table fits the copy (whole_tab: else the table copy is written per round
+//                and the read is not shared) is published after the prologue's last LDS write: a workgroup release fence by every
+//                lane (each wrote part of the data), then lane 0's descriptor stores, its release fence, and one atomic store of
+//                the wave's claim word {next round = 1 | rounds << 16}.
+//   claims       A round is claimed by an LDS atomic add of 1 on the claim word; the old value names the round if its low half is below
+//                the high half.  The owner claims the same way, between a round's walk and its sums (list[] of its next round
+//                travels behind the sums, as before); round 0 is always its own (its records are asked for in the prologue, and the
+//                list[] entries parked in its slots die with its first walk).  A helper reads the word first and adds only where a
+//                round is open, so a word over-counts by at most the block's waves (rounds < 2^15: the halves do not meet).  After a
+//                claim the helper makes an acquire fence, reads the descriptor, asks for list[] of the round and then its records.
+//   helpers      `busy` counts the block's waves that have not drawn dry.  A dry wave polls its block-mates' claim words -- never its
+//                own -- with s_sleep F5_HELP_NAP between looks, and leaves when busy == 0 (an owner draws dry only after every round
+//                of its read is claimed, or its word is closed: nothing is open then) or F5_HELP_CAP ticks of the constant 100 MHz
+//                counter (20 ms) after it drew dry.
+//   closing      A word is open only while its read is the one in the owner's LDS object.  A read that goes through uses its word
+//                up (the owner's last claim finds no round left).  An owner that leaves a published read EARLY -- a round of its
+//                own turned the read down -- stores 0 into its word before it draws: left open, the word would outlive a draw
+//                that hands out a read, and a wave that drew dry later would score the dead read's rounds over the new read's data.
+// NO WAVE EVER WAITS FOR ANOTHER TO DO SOMETHING.  An owner does not wait for helpers: it claims until its word is used up, scores what
+// it claimed, and goes on to draw.  A helper may leave at any moment: what nobody claimed the owner scores.  A helper's reads of an
+// owner's LDS object are safe without any wait, because the queue's counter only grows: once any wave of the launch has drawn dry
+// (n_waves + counter >= n_reads; a wave whose own number is past the last read implies n_waves >= n_reads), every later draw is dry
+// too -- the helper's dry draw returned before it claimed, the owner's next draw is issued after its own last claim or after it closed
+// its word -- so an owner never runs another prologue while a helper that claimed from its word can be reading its object, and after
+// that draw the word gives nothing out; and a block's LDS lives until its last wave leaves, after the helper.  There is no waiting across blocks, no barrier after the first, no spin without the cap.  What ends a round early (a
+// record outside the compact form: *n_unhandled, which the drivers test for > 0) or marks the read (ST_FAIL) a helper records as the
+// owner would, and goes on polling.  Rounds a helper SCORED (not those it was turned down in) are counted in *shared_rounds, one
+// atomic each (the tail pays it).
+// $SK_F5_SHARE=0 (FusedScoreArgs::share = 0): nothing is published, a dry wave leaves at once, the kernel runs as it did.
+constexpr int F5_HELP_NAP = 64; // s_sleep between a dry wave's looks: ~4 000 cycles, under 2 us -- a fifth of a round
+constexpr unsigned F5_HELP_CAP = 2000000u; // ticks of the 100 MHz counter a dry wave stays at most: 20 ms
 template <int MAXR, bool TIMING, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 4))) void flatten_score_kernel(const FusedScoreArgs fa, const int n_reads)
 {
     __shared__ __attribute__((aligned(16))) F5Lds<MAXR> S[WAVES];
     // the two terms of every quality, once per block (every wave reaches the barrier: it stands before the first draw)
     __shared__ double q_terms[F5_Q_TERMS];
+    __shared__ F5Share share[WAVES];
+    __shared__ unsigned busy;
     for (int i = threadIdx.x; i < F5_Q_TERMS; i += 64 * WAVES) q_terms[i] = (i <= SK_NQ) ? fa.tab->q2lncompe[i] : fa.tab->q2mis[i - (SK_NQ + 1)];
+    if (threadIdx.x < unsigned(WAVES)) share[threadIdx.x].claim = 0u, share[threadIdx.x].dry_at = 0u; // (nothing open, nobody dry)
+    if (threadIdx.x == 0) busy = unsigned(WAVES);
     __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)), lane = threadIdx.x & 63;
     const unsigned n_waves = gridDim.x * unsigned(WAVES);
+    // a read of `ncr` candidate alignments is published: sharing is on, the job's table fits the copy, more than one round
+    auto published = [&](const int ncr) -> bool { return WAVES > 1 && fa.share != 0 && fa.f.job.n_tab <= F5_TAB && ncr > 64 && ncr < (0x8000 << 6); };
     // the first hand-out: the wave's own number, no draw
     unsigned h = unsigned(__builtin_amdgcn_readfirstlane(int(blockIdx.x * unsigned(WAVES) + unsigned(wave))));
     unsigned long long draw_cycles = 0;
-    while (h < unsigned(n_reads)) {
-        // hand-out h is read h, except among the launch's last tail_n hand-outs, which go through the table (the same for the whole
-        // wave; one more dependent load, paid by those hand-outs only)
-        unsigned r = h;
-        if (h - fa.tail_first < fa.tail_n) r = unsigned(__builtin_amdgcn_readfirstlane(fa.tail_order[h - fa.tail_first]));
-        f5_read<MAXR, TIMING>(fa, int(r), S[wave], q_terms, draw_cycles);
+    auto draw = [&]() {
         f5_wave_sync(); // (the wave's LDS object is the next read's)
         const unsigned long long t0 = TIMING ? (unsigned long long)clock64() : 0ull;
-        unsigned d = 0;
-        if (lane == 0) d = atomicAdd(&fa.queue[0], 1u);
-        int drawn = __builtin_amdgcn_readfirstlane(int(d));
+        unsigned got = 0;
+        if (lane == 0) got = atomicAdd(&fa.queue[0], 1u);
+        int drawn = __builtin_amdgcn_readfirstlane(int(got));
         if (TIMING) __asm__ volatile("" : "+s"(drawn)); // (the second stamp stands after the value has arrived)
         h = n_waves + unsigned(drawn);
         draw_cycles = TIMING ? (unsigned long long)clock64() - t0 : 0ull;
+    };
+    F5Desc d; // the read whose round comes next: the wave's own, or a block-mate's
+    F5Own own;
+    d.r = d.c0 = d.ncr = d.L = d.P = d.win_begin = d.sorted_order = 0;
+    int j = -1, src = wave; // the round to run (-1: none); the wave whose LDS object holds the read (the wave's own: it is the owner)
+    for (;;) {
+        if (j < 0 && h < unsigned(n_reads)) { // ---- the owner's next read
+            // hand-out h is read h, except among the launch's last tail_n hand-outs, which go through the table (the same for the whole
+            // wave; one more dependent load, paid by those hand-outs only)
+            unsigned r = h;
+            if (h - fa.tail_first < fa.tail_n) r = unsigned(__builtin_amdgcn_readfirstlane(fa.tail_order[h - fa.tail_first]));
+            if (!f5_prologue<MAXR, TIMING>(fa, int(r), S[wave], q_terms, d, own)) {
+                draw();
+                continue;
+            }
+            j = 0;
+            if (published(d.ncr)) {
+                // (every lane wrote part of the prologue's data: every lane releases its stores, before lane 0 alone writes the
+                // descriptor and, behind a release of its own, the word)
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                __builtin_amdgcn_wave_barrier();
+                if (lane == 0) {
+                    share[wave].d = d;
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                    __hip_atomic_store(&share[wave].claim, 1u | (unsigned((d.ncr + 63) >> 6) << 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+            }
+        } else if (j < 0) { // ---- a dry wave (h is past the last read and stays there: no further draw): a round of a block-mate's read
+            // (when it drew dry is kept in LDS, and the lane is taken anew: neither is a register's through the owners' rounds)
+            unsigned dry_at = unsigned(__builtin_amdgcn_readfirstlane(int(share[wave].dry_at)));
+            if (dry_at == 0u) {
+                if (lane == 0) __hip_atomic_fetch_add(&busy, ~0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (!(WAVES > 1 && fa.share != 0)) break;
+                dry_at = unsigned(wall_clock64()) | 1u;
+                if (lane == 0) share[wave].dry_at = dry_at;
+            }
+            int look = threadIdx.x & 63;
+            __asm__ volatile("" : "+v"(look));
+            unsigned w = 0;
+            if (look < WAVES && look != wave) w = __hip_atomic_load(&share[look].claim, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); // (never its own)
+            const unsigned long long open = __ballot((w & 0xffffu) < (w >> 16));
+            if (open == 0ull) {
+                const unsigned left = __hip_atomic_load(&busy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (__builtin_amdgcn_readfirstlane(int(left)) == 0 || unsigned(wall_clock64()) - dry_at > F5_HELP_CAP) break;
+                __builtin_amdgcn_s_sleep(F5_HELP_NAP);
+                continue;
+            }
+            const int o = __builtin_amdgcn_readfirstlane(__builtin_ctzll(open)); // (< WAVES: only those lanes looked)
+            unsigned old = 0;
+            if (lane == 0) old = __hip_atomic_fetch_add(&share[o].claim, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            old = unsigned(__builtin_amdgcn_readfirstlane(int(old)));
+            if ((old & 0xffffu) >= (old >> 16)) continue; // (taken meanwhile: look again)
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            const F5Desc& p = share[o].d;
+            d.r = __builtin_amdgcn_readfirstlane(p.r), d.c0 = __builtin_amdgcn_readfirstlane(p.c0), d.ncr = __builtin_amdgcn_readfirstlane(p.ncr);
+            d.L = __builtin_amdgcn_readfirstlane(p.L), d.P = __builtin_amdgcn_readfirstlane(p.P);
+            d.win_begin = __builtin_amdgcn_readfirstlane(p.win_begin), d.sorted_order = __builtin_amdgcn_readfirstlane(p.sorted_order);
+            j = int(old & 0xffffu), src = o;
+            // (what the owner gets a round ahead: list[] of the round; a lane without an alignment names record 0, which nothing looks at)
+            own.slot_next = (64 * j + lane < d.ncr) ? fa.f.list[f5_list_index(S[src], d, 64 * j + lane)] : 0;
+            own.my_ins_idx = -1, own.my_ins_off = 0;
+        }
+        const bool mine = src == wave;
+        int j_next = -1;
+        const bool went = f5_round<MAXR, TIMING>(
+            fa, S[src], S[wave].slot, d, j, mine, own,
+            [&]() -> int { // the owner's next round: the one after this, or, of a published read, the next that nobody has claimed
+                int nj = j + 1;
+                if (published(d.ncr)) {
+                    unsigned old = 0;
+                    if (lane == 0) old = __hip_atomic_fetch_add(&share[wave].claim, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    nj = __builtin_amdgcn_readfirstlane(int(old)) & 0xffff;
+                }
+                return 64 * nj < d.ncr ? nj : -1;
+            },
+            j_next);
+        if (!mine && went && lane == 0) atomicAdd(fa.shared_rounds, 1u); // (a helped round that was scored)
+        j = (mine && went) ? j_next : -1;
+        if (mine && j < 0) { // (the owner's last round, or the round that left the read to the staged chain)
+            if (went) f5_store_stamps<TIMING>(fa, d.r, own, draw_cycles);
+            // The owner leaves a published read EARLY: it closes its word before it draws.  A round claimed before the store is a
+            // helper's, and a helper has drawn dry, so the draw below is dry too (the argument above); after the store nothing can be
+            // claimed, and if the draw hands out a read, its prologue writes an object that no word points at.  (A read that went
+            // through needs no store: its word is used up, the owner's last claim found it so.)
+            else if (published(d.ncr) && lane == 0) __hip_atomic_store(&share[wave].claim, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            draw();
+        }
     }
     if (lane == 0) {
         __threadfence();
@@ -2456,6 +2673,8 @@ namespace
 // an assumption of the sequence did not hold (deeper levels than launched, a full leaf pool, a read outside F5's form)
 int64_t g_jobs_one_wait = 0, g_jobs_one_wait_redone = 0, g_jobs_staged = 0;
 int64_t g_tail_launches = 0; // launches of tail_order_kernel by the job drivers (sk_debug_f5_tail_launches)
+int64_t g_late_turn_downs = 0; // F5's rounds after a read's first that left the read to the staged chain, over the drivers' F5 launches
+int64_t g_shared_rounds = 0; // F5's rounds scored by a wave other than their read's owner, over the drivers' jobs (sk_debug_f5_shared_rounds)
 // diagnostics ($SK_ENUM_JOB_SECONDS): where a one-sequence job's wall time goes -- buffers + packing, submissions, the wait -- on stderr at exit
 struct JobSeconds
 {
@@ -2510,6 +2729,8 @@ extern "C" int sk_debug_f5_tail_order(const int32_t* cal_off, const int32_t n_re
     return rc;
 }
 extern "C" int64_t sk_debug_f5_tail_launches(void) { return g_tail_launches; }
+extern "C" int64_t sk_debug_f5_shared_rounds(void) { return g_shared_rounds; }
+extern "C" int64_t sk_debug_f5_late_turn_downs(void) { return g_late_turn_downs; }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // the job driver.  A job is prepared once (start_job, plan_job: capacities, the arenas' layout, reservations, the packed input on its way up)
@@ -2875,6 +3096,10 @@ FusedScoreArgs fused_args(const JobPlan& p, const FlatArgs& fa)
     fs.dbg = nullptr;
     fs.tail_order = nullptr; // (plan_tail)
     fs.tail_first = fs.tail_n = 0;
+    // $SK_F5_SHARE = 0: no round sharing (experiments and tests; read once)
+    static const bool share = [] { const char* e = std::getenv("SK_F5_SHARE"); return !(e && std::strcmp(e, "0") == 0); }();
+    fs.share = share ? 1 : 0;
+    fs.shared_rounds = B.counters.as<unsigned>() + CNT_SHARED;
     return fs;
 }
 
@@ -3084,6 +3309,8 @@ int run_one_wait(const JobPlan& p, SkEnumOutput* out, bool* redo)
     p.lap("one sequence");
     const int32_t* h_counters = B.h_counters.as<int32_t>();
     const int32_t* const h_dyn = h_counters + CNT_DYN;
+    g_shared_rounds += h_counters[CNT_SHARED]; // (of this launch, whether the job is run again or not)
+    g_late_turn_downs += h_counters[CNT_SHARED + 1];
     if (h_dyn[DYN_FLAGS] != 0 || h_counters[CNT_UNHANDLED] > 0) {
         if (p.timing)
             std::fprintf(stderr, "[enum-dev] one sequence: flags %d, reads outside F5's form %d -> the staged chain\n", h_dyn[DYN_FLAGS], h_counters[CNT_UNHANDLED]);
@@ -3369,6 +3596,8 @@ int run_staged(const JobPlan& p, SkEnumOutput* out)
     SK_HIP(skrt::streamSynchronize(st));
     // (when F5 turned a read down both chains filled the pools: the count may be double -- what matters to the caller is zero or not)
     out->ref_reads_outside = B.h_counters.as<int32_t>()[CNT_DYN + DYN_REF_OUTSIDE];
+    g_shared_rounds += B.h_counters.as<int32_t>()[CNT_SHARED]; // (the job's one F5 launch, if it had one: the counters' last fetch)
+    g_late_turn_downs += B.h_counters.as<int32_t>()[CNT_SHARED + 1];
     p.lap("done");
     return 0;
 }
@@ -3405,11 +3634,26 @@ static int f5_timing_report(hipStream_t st)
     unsigned long long* d = dbg.as<unsigned long long>();
     SK_HIP(skrt::memsetAsync(d, 0, nb * 8, st));
     fs.dbg = d;
+    unsigned helped[2] = { 0, 0 }; // the job's count of helped rounds before and after this launch
+    SK_HIP(skrt::memcpyAsync(&helped[0], fs.shared_rounds, 4, hipMemcpyDeviceToHost, st));
     launch_flatten_score(g_last.n, st, fs);
+    SK_HIP(skrt::memcpyAsync(&helped[1], fs.shared_rounds, 4, hipMemcpyDeviceToHost, st));
     std::vector<unsigned long long> h(nb);
     SK_HIP(skrt::memcpyAsync(h.data(), d, nb * 8, hipMemcpyDeviceToHost, st));
     SK_HIP(skrt::streamSynchronize(st));
     dbg.drop();
+    { // the rounds of the reads that were scored (a stamped read: its owner went through all it claimed), by who scored them
+        const int32_t* const cal_off = bufs().h_cal_off.as<int32_t>();
+        long long by_owner = 0, implied = 0;
+        for (int r = 0; r < g_last.n; ++r) {
+            const unsigned long long* s = &h[size_t(r) * F5_STAMPS];
+            if (s[6] == 0) continue;
+            by_owner += (long long)s[10];
+            implied += (cal_off[r + 1] - cal_off[r] + 63) / 64;
+        }
+        std::fprintf(stderr, "[f5-timing] rounds: %lld scored by their owners + %u by helpers = %lld; cal_off implies %lld (sharing %s)\n", by_owner,
+                     helped[1] - helped[0], by_owner + (long long)(helped[1] - helped[0]), implied, fs.share ? "on" : "off");
+    }
     double sum[F5_STAMPS] = { 0 };
     unsigned long long first = ~0ull, last = 0;
     int nblk = 0, ndrawn = 0;
