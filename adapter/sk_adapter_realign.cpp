@@ -220,7 +220,7 @@ void realign_sample_window(starling_pos_processor_base& pp, const unsigned sampl
     ro.min_read_bp_flank = sif.sampleOptions.min_read_bp_flank;
     ro.sample_count = static_cast<int32_t>(sampleCount);
     // Every job's search, flattening, scoring and stage 3 run on the device (enumeration 2): as ONE fixed sequence of launches with one
-    // host wait (csrc/read_enumerate.hip, job_scan_kernel), staged in and out by kernels, with the window of the reference its reads can
+    // host wait (csrc/read_enumerate.hip; job_scan_kernel, csrc/enum_search.h), staged in and out by kernels, with the window of the reference its reads can
     // reach.  In that form a job costs less inside the C-ABI than the host statement of the search + one scoring launch did, alone on a
     // GPU (0.25 against 0.33 ms) and with eight caller processes sharing it (0.35 against 0.39 ms; profiles/r05_enum_job_history.txt) --
     // round 4's three-wait form, with the whole contig segment copied and uploaded per job, cost 0.56 ms and the adapter kept jobs under

@@ -313,7 +313,7 @@ typedef struct sk_realign_options { /* L/starling_common/starling_base_shared.hh
                                              0 = host, container-based statement (the one pinned to the reference);
                                              1 = host, the container-free core of csrc/realign_core.h (what the device runs);
                                              2 = device: search, ordering / de-duplication and flattening of every read's
-                                                 candidate alignments in kernels (csrc/read_enumerate.hip), scored where they
+                                                 candidate alignments in kernels (csrc/read_enumerate.hip, csrc/enum_*.h), scored where they
                                                  are; reads beyond the core's fixed capacities take path 0.
                                              sk_realign_options_default: 2 once sk_init has succeeded, else 0; the
                                              environment variable SK_ENUMERATION overrides the default.

@@ -1,5 +1,5 @@
 // read_enumerate.h -- internal interface between the host stages of the realignment job (host/read_realign.cpp) and the device
-// enumeration pipeline (csrc/read_enumerate.hip): sk_realign_options.enumeration == 2.
+// enumeration pipeline (csrc/read_enumerate.hip: the driver; its kernels in the sections csrc/enum_*.h): sk_realign_options.enumeration == 2.
 //
 // Only what the reference's getCandidateAlignments hands to candidate_alignment_search crosses PCIe on the way in (PRead: start
 // alignment, indel status map, indel order, observed indels) plus the read bases/qualities, the indel table and the reference

@@ -1303,7 +1303,7 @@ void get_candidate_alignments(const Job& job, sk_realign_job::Read& rd, const st
         job.n_fallback_reads.fetch_add(1, std::memory_order_relaxed);
     }
     if (job.opt.enumeration == 1) {
-        // the container-free core, on this thread (enumeration == 2 runs the same code on the device, read_enumerate.hip)
+        // the container-free core, on this thread (enumeration == 2 runs the same code on the device, csrc/enum_search.h)
         std::unique_ptr<skcore::PRead> pr(new skcore::PRead);
         if (to_core_read(job, observed, rd.sample, cal_read_length, realign_range, exemplar_pr, sm, order, cal, *pr)) {
             CoreTables tables;
@@ -2270,7 +2270,7 @@ static int finish_builder(sk_realign_job* j, sk_align_batch* out)
 
 } // extern "C"
 
-// ---- stage 3 in its container-free form (csrc/stage3_core.h; the device runs the same code, read_enumerate.hip) ----
+// ---- stage 3 in its container-free form (csrc/stage3_core.h; the device runs the same code, csrc/enum_stage3.h) ----
 struct Stage3Tables
 {
     CoreTables core;

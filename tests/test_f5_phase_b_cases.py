@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from strelka_amd import capi, synth
-from tests import test_read_realign as T
+from tests import f5_util as U
 
 _BASES = "ACGT"
 
@@ -51,30 +51,17 @@ def test_f5_equals_staged_and_host(seed, read_len, window, monkeypatch):
     scs = _scenarios(seed, read_len, window, 24)
     n_cals, n_reads, n_jobs, n_f5_jobs, n_clip, lens = [], 0, 0, 0, 0, []
     for sc in scs:
-        res = {}
-        for chain in ("host", "staged", "f5"):
-            monkeypatch.setenv("SK_A5_FUSED", "0" if chain == "staged" else "1")
-            monkeypatch.setenv("SK_ENUM_ONE_WAIT", "1")
-            before = capi.RealignJob.device_job_counts()
-            job = capi.RealignJob(capi.realign_options(is_haplotyping_enabled=sc["is_haplotyping_enabled"],
-                                                       min_read_bp_flank=sc["min_read_bp_flank"],
-                                                       enumeration=0 if chain == "host" else 2))
-            job.set_reference(sc["ref_seq"], sc["ref_offset"])
-            job.set_indels(sc["indels"])
-            idx = T._add_reads(job, sc)
-            job.run()
-            got = [None if i is None else job.result(i) for i in idx]
-            res[chain] = [repr(x) for x in got]
-            if chain == "f5":
-                n_cals += [x["n_cals"] for x in got if x is not None]
-                counts = job.enumeration_counts()
-                one_wait, redone, staged = (b - a for a, b in zip(before, capi.RealignJob.device_job_counts()))
-                if counts[1] > 0:
-                    # F5 took every read of the job (one fixed sequence, nothing left to the staged chain), or turned one down and the
-                    # job ran again the staged way
-                    assert (one_wait, redone, staged) in ((1, 0, 0), (0, 1, 1)), (one_wait, redone, staged)
-                    n_jobs += 1
-                    n_f5_jobs += one_wait
+        out = {chain: U.run_chain(sc, chain, setenv=monkeypatch.setenv) for chain in ("host", "staged", "f5")}
+        res = {chain: out[chain]["res"] for chain in out}
+        f5, idx = out["f5"], out["f5"]["idx"]
+        n_cals += [x["n_cals"] for x in f5["got"] if x is not None]
+        one_wait, redone, staged = f5["jobs"]
+        if f5["counts"][1] > 0:
+            # F5 took every read of the job (one fixed sequence, nothing left to the staged chain), or turned one down and the
+            # job ran again the staged way
+            assert (one_wait, redone, staged) in ((1, 0, 0), (0, 1, 1)), (one_wait, redone, staged)
+            n_jobs += 1
+            n_f5_jobs += one_wait
         assert res["f5"] == res["host"]
         assert res["staged"] == res["host"]
         for rd, r in zip(sc["reads"], idx):

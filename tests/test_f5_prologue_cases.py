@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 
 from strelka_amd import capi, synth
-from tests import test_read_realign as T
+from tests import f5_util as U
 
 _BASES = "ACGT"
 _INS_REGS = 4      # inserts the prologue keeps in registers (F5_INS_REG)
@@ -79,23 +79,6 @@ def _scenarios(seed, read_len, window, n):
     return scs
 
 
-def _run(sc, chain, monkeypatch):
-    monkeypatch.setenv("SK_A5_FUSED", "0" if chain == "staged" else "1")
-    monkeypatch.setenv("SK_ENUM_ONE_WAIT", "1")
-    before = capi.RealignJob.device_job_counts()
-    outside0 = capi.lib().sk_realign_reference_reads_outside()
-    job = capi.RealignJob(capi.realign_options(is_haplotyping_enabled=sc["is_haplotyping_enabled"],
-                                               min_read_bp_flank=sc["min_read_bp_flank"], enumeration=0 if chain == "host" else 2))
-    job.set_reference(sc["ref_seq"], sc["ref_offset"])
-    job.set_indels(sc["indels"])
-    idx = T._add_reads(job, sc)
-    job.run()
-    got = [None if i is None else job.result(i) for i in idx]
-    return dict(res=[repr(x) for x in got], got=got, idx=idx, consulted=job.indels_consulted().tolist(),
-                outside=capi.lib().sk_realign_reference_reads_outside() - outside0, counts=job.enumeration_counts(),
-                jobs=tuple(b - a for a, b in zip(before, capi.RealignJob.device_job_counts())))
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("seed,read_len,window", [(96201, (30, 153), (200, 360)), (96202, (153, 257), (330, 430))])
 def test_f5_prologue_equals_staged_and_host(seed, read_len, window, monkeypatch):
@@ -105,8 +88,8 @@ def test_f5_prologue_equals_staged_and_host(seed, read_len, window, monkeypatch)
     seen = dict(left=0, right=0, no_insert=0, insert_stretch=0, small_table=0, big_table=0)
     byte_off, residues, lens = set(), set(), []
     for sc in scs:
-        out = {chain: _run(sc, chain, monkeypatch) for chain in ("host", "staged", "f5")}
-        out["again"] = _run(sc, "f5", monkeypatch)
+        out = {chain: U.run_chain(sc, chain, setenv=monkeypatch.setenv) for chain in ("host", "staged", "f5")}
+        out["again"] = U.run_chain(sc, "f5", setenv=monkeypatch.setenv)
         f5 = out["f5"]
         print(sc["kind"], "jobs", f5["jobs"], "outside", [out[c]["outside"] for c in out], "consulted", sum(f5["consulted"]),
               "of", len(sc["indels"]))

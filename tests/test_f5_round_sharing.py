@@ -24,7 +24,6 @@ process, so every shape is a child process of this file.
    draws dry later scores the dead read's rounds over another read's data.  The job falls to the staged chain and equals the host's
    results, consulted flags and count of reference reads outside."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -35,31 +34,18 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from strelka_amd import capi  # noqa: E402
-from tests import test_f5_prologue_cases as P  # noqa: E402
+from tests import f5_util as U  # noqa: E402
+from tests import test_f5_prologue_cases as P  # noqa: E402  (scenario builders: here, and test_f5_phase_b_cases below)
 from tests import test_f5_tail_order as T  # noqa: E402
 
 _SHAPES = [  # (SK_F5_GRID, SK_F5_WAVES, SK_F5_TAIL_SHIFT, form)
     (1, 1, 0, 152), (1, 2, 0, 152), (1, 8, 0, 152), (2, 8, 3, 152), (1, 16, 0, 152), (1, 4, 1, 256), (3, 4, 0, 256)]
 
 
-def _run(sc, chain, reads, **kw):
-    """T._run, with the helped rounds of the job"""
-    before = capi.RealignJob.f5_shared_rounds()
-    out = T._run(sc, chain, reads, **kw)
-    out["shared"] = capi.RealignJob.f5_shared_rounds() - before
-    return out
-
-
-def _same(a, b, what):
-    assert a["res"] == b["res"], what
-    assert a["consulted"] == b["consulted"], what
-    assert a["outside"] == b["outside"], what
-
-
 def _distinct(form):
     """the scenario, its distinct reads' host results and their candidate-alignment counts"""
     sc = T._tail_scenario(form == 256)
-    one = _run(sc, "host", sc["reads"])
+    one = U.run_chain(sc, "host", sc["reads"])
     assert all(r is not None for r in one["res"])
     n_cals = [eval(r, {"nan": float("nan"), "inf": float("inf")})["n_cals"] for r in one["res"]]
     print("candidate alignments of the distinct reads", n_cals, "outside", one["outside"])
@@ -69,15 +55,6 @@ def _distinct(form):
     longest = max(len(rd["code"]) for rd in sc["reads"])
     assert longest == 160 if form == 256 else longest <= 152
     return sc, one, n_cals
-
-
-def _fresh_f5(sc, reads, **kw):
-    """an F5 job that does not follow a job of its own layout (the scores are not cleared between jobs: a round nobody scored would
-    still find its right scores after an identical job) -- the same reads in reverse order go first"""
-    first = _run(sc, "f5", reads[::-1])
-    out = _run(sc, "f5", reads, **kw)
-    out["shared"] += first["shared"]
-    return out
 
 
 def _child(mode, form):
@@ -102,13 +79,13 @@ def _child(mode, form):
 
         for n in sorted({1, 2, w - 1, w, w + 1, 2 * w + 3} - {0}):
             reads, want = job_of(n)
-            f5 = _fresh_f5(sc, reads)
-            host, staged = _run(sc, "host", reads), _run(sc, "staged", reads)
-            again = _fresh_f5(sc, reads, rescore=2)
+            f5 = U.fresh_f5(sc, reads)
+            host, staged = U.run_chain(sc, "host", reads), U.run_chain(sc, "staged", reads)
+            again = U.fresh_f5(sc, reads, rescore=2)
             print("reads", n, "jobs", f5["jobs"], again["jobs"], "helped rounds", f5["shared"], again["shared"], "outside", host["outside"])
             assert host["res"] == want and f5["counts"][1] == again["counts"][1] == n
             for got, what in ((staged, "staged"), (f5, "f5"), (again, "again")):
-                _same(got, host, (n, what))
+                U.assert_same(got, host, (n, what))
             assert f5["jobs"] == (1, 0, 0) and again["jobs"] == (1, 0, 0)
             assert host["shared"] == 0 and staged["shared"] == 0
             total += f5["shared"] + again["shared"]
@@ -116,23 +93,23 @@ def _child(mode, form):
         for target in (65, 128, 129):
             i = min(range(k), key=lambda q: (abs(n_cals[q] - target), q))
             reads = [sc["reads"][i]]
-            f5, host, staged = _fresh_f5(sc, reads), _run(sc, "host", reads), _run(sc, "staged", reads)
+            f5, host, staged = U.fresh_f5(sc, reads), U.run_chain(sc, "host", reads), U.run_chain(sc, "staged", reads)
             print("nearest to", target, "candidate alignments:", n_cals[i], "helped rounds", f5["shared"])
             assert host["res"] == [one["res"][i]]
-            _same(f5, host, target)
-            _same(staged, host, target)
+            U.assert_same(f5, host, target)
+            U.assert_same(staged, host, target)
             assert f5["jobs"] == (1, 0, 0)
             total += f5["shared"]
     elif mode == "big_table":
         # the scenario's own job first: sharing works in this process (the counter moves), so that standing still below says something
         reads = [sc["reads"][i] for i in sorted(range(k), key=lambda i: -n_cals[i])[:2]] * 3
         for _ in range(3):
-            total += _fresh_f5(sc, reads)["shared"]
+            total += U.fresh_f5(sc, reads)["shared"]
         big = [s for s in P._scenarios(96201, (30, 153), (200, 360), 6) if s["kind"] == "big_table"][0]
         assert len(big["indels"]) > P._TAB
-        f5, host = _fresh_f5(big, big["reads"]), _run(big, "host", big["reads"])
+        f5, host = U.fresh_f5(big, big["reads"]), U.run_chain(big, "host", big["reads"])
         print("big table:", len(big["indels"]), "entries,", len(big["reads"]), "reads, jobs", f5["jobs"], "helped rounds", f5["shared"])
-        _same(f5, host, "big table")
+        U.assert_same(f5, host, "big table")
         assert f5["shared"] == 0
     elif mode == "turned_down":
         from tests import test_f5_phase_b_cases as B
@@ -140,7 +117,7 @@ def _child(mode, form):
         found = None
         for i, cand in enumerate(B._scenarios(95102, (153, 257), (330, 430), 24)):
             at = late()
-            got = _run(cand, "f5", cand["reads"])
+            got = U.run_chain(cand, "f5", cand["reads"])
             print("scenario", i, "reads", got["counts"][1], "jobs", got["jobs"], "late turn-downs", late() - at)
             if late() > at and found is None:
                 found = cand
@@ -148,7 +125,7 @@ def _child(mode, form):
         bad = []
         for i, rd in enumerate(found["reads"]):
             at = late()
-            _run(found, "f5", [rd])
+            U.run_chain(found, "f5", [rd])
             if late() > at:
                 bad.append(i)
         print("reads turned down in a later round:", bad)
@@ -159,13 +136,13 @@ def _child(mode, form):
             while len(reads) < 3 * w + 1:
                 reads.append(rest[len(reads) % len(rest)])
             at = late()
-            f5 = _run(found, "f5", reads)
+            f5 = U.run_chain(found, "f5", reads)
             moved = late() - at
-            host, staged = _run(found, "host", reads), _run(found, "staged", reads)
+            host, staged = U.run_chain(found, "host", reads), U.run_chain(found, "staged", reads)
             print("job of", len(reads), "reads, read", first, "first: jobs", f5["jobs"], "late turn-downs", moved, "helped rounds", f5["shared"])
             assert moved > 0 and f5["jobs"] == (0, 1, 1)
-            _same(f5, host, ("turned down", first))
-            _same(staged, host, ("turned down, staged", first))
+            U.assert_same(f5, host, ("turned down", first))
+            U.assert_same(staged, host, ("turned down, staged", first))
             total += f5["shared"]
         total = 0 if not share_on else total
     print("SHARED", total)
@@ -175,15 +152,7 @@ def _child(mode, form):
 
 
 def _spawn(mode, grid, waves, shift, form, share=None):
-    env = dict(os.environ, SK_F5_GRID=str(grid), SK_F5_WAVES=str(waves), SK_F5_TAIL_SHIFT=str(shift))
-    env.pop("SK_F5_SHARE", None)
-    if share is not None:
-        env["SK_F5_SHARE"] = share
-    p = subprocess.run([sys.executable, os.path.abspath(__file__), mode, str(form)], env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                       timeout=300)
-    out = p.stdout.decode(errors="replace")
-    print(out[-3000:])
-    assert p.returncode == 0 and "SHARE-CHILD-OK" in out, out[-3000:]
+    out = U.spawn_child(__file__, mode, form, "SHARE-CHILD-OK", SK_F5_GRID=grid, SK_F5_WAVES=waves, SK_F5_TAIL_SHIFT=shift, SK_F5_SHARE=share)
     return int([ln for ln in out.splitlines() if ln.startswith("SHARED ")][-1].split()[1])
 
 

@@ -18,9 +18,7 @@
    counts say F5 scored the job itself; and the table kernel was launched exactly for the jobs with n > W and s > 0.
 3. The one-sequence and the staged driver give the same for such a job, each with one launch of the table kernel, and none for a
    job that fits the grid."""
-import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -31,7 +29,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from strelka_amd import capi, synth  # noqa: E402
-from tests import test_f5_turn_ahead_cases as Q  # noqa: E402
+from tests import f5_util as U  # noqa: E402
+from tests import test_f5_turn_ahead_cases as Q  # noqa: E402  (its scenario builders)
 
 _CALS = (0, 1, 63, 64, 65, 128, 129, 256, 257, 400)
 
@@ -144,24 +143,6 @@ def _tail_scenario(long_read):
     return sc
 
 
-def _run(sc, chain, reads, one_wait="1", rescore=0):
-    os.environ["SK_A5_FUSED"] = "0" if chain == "staged" else "1"
-    os.environ["SK_ENUM_ONE_WAIT"] = one_wait
-    before = capi.RealignJob.device_job_counts()
-    launches0 = capi.RealignJob.f5_tail_launches()
-    outside0 = capi.lib().sk_realign_reference_reads_outside()
-    job = Q._job(sc, 0 if chain == "host" else 2)
-    idx = Q._add(job, reads)
-    job.run()
-    if rescore:
-        ms, nr, nc, cells = C.c_float(0), C.c_int32(0), C.c_int32(0), C.c_int64(0)
-        assert capi.lib().sk_realign_job_rescore(rescore, C.byref(ms), C.byref(nr), C.byref(nc), C.byref(cells)) == 0, capi.last_error()
-    res = [None if i is None else repr(job.result(i)) for i in idx]
-    return dict(res=res, consulted=job.indels_consulted().tolist(), counts=job.enumeration_counts(), outside=capi.lib().sk_realign_reference_reads_outside() - outside0,
-                jobs=tuple(b - a for a, b in zip(before, capi.RealignJob.device_job_counts())),
-                launches=capi.RealignJob.f5_tail_launches() - launches0)
-
-
 def _child(mode, form):
     grid, waves, shift = (int(os.environ[k]) for k in ("SK_F5_GRID", "SK_F5_WAVES", "SK_F5_TAIL_SHIFT"))
     capi.init(0)
@@ -169,7 +150,7 @@ def _child(mode, form):
     k = len(sc["reads"])
     w = grid * waves
     t = w + 6 * shift
-    one = _run(sc, "host", sc["reads"])
+    one = U.run_chain(sc, "host", sc["reads"])
     assert all(r is not None for r in one["res"])
     n_cals = [eval(r, {"nan": float("nan"), "inf": float("inf")})["n_cals"] for r in one["res"]]
     print("candidate alignments of the distinct reads", n_cals, "outside", one["outside"])
@@ -185,23 +166,12 @@ def _child(mode, form):
             idx.append(len(idx) % k)
         return [sc["reads"][i] for i in idx], [one["res"][i] for i in idx]
 
-    def fresh_f5(reads, **kw):
-        """an F5 job that does not follow a job of its own layout: the scores are not cleared between jobs, and after an identical job
-        a read that a hand-out skipped would still find its right scores there -- so the same reads in reverse order go first"""
-        _run(sc, "f5", reads[::-1])
-        return _run(sc, "f5", reads, **kw)
-
-    def same(a, b, what):
-        assert a["res"] == b["res"], what
-        assert a["consulted"] == b["consulted"], what
-        assert a["outside"] == b["outside"], what
-
     if mode == "drivers":
         for n, table in ((2 * t + 5, 1), (w, 0)):
             reads, want = tiled(n)
-            a, b = fresh_f5(reads, one_wait="1"), fresh_f5(reads, one_wait="0")
+            a, b = U.fresh_f5(sc, reads, one_wait="1"), U.fresh_f5(sc, reads, one_wait="0")
             print("reads", n, "one sequence", a["jobs"], a["launches"], "staged driver", b["jobs"], b["launches"])
-            same(a, b, n)
+            U.assert_same(a, b, n)
             assert a["res"] == want and a["counts"][1] == b["counts"][1] == n
             assert a["jobs"] == (1, 0, 0) and b["jobs"] == (0, 0, 1)
             assert a["launches"] == table and b["launches"] == table
@@ -209,13 +179,13 @@ def _child(mode, form):
         return
     for n in sorted({w - 1, w, w + 1, w + shift + 1, t, t + 1, 2 * t + 5} - {0}):
         reads, want = tiled(n)
-        f5 = fresh_f5(reads)
-        host, staged = _run(sc, "host", reads), _run(sc, "staged", reads)
-        again = fresh_f5(reads, rescore=2)
+        f5 = U.fresh_f5(sc, reads)
+        host, staged = U.run_chain(sc, "host", reads), U.run_chain(sc, "staged", reads)
+        again = U.fresh_f5(sc, reads, rescore=2)
         print("reads", n, "jobs", f5["jobs"], again["jobs"], "table launches", f5["launches"], again["launches"], "outside", host["outside"])
         assert host["res"] == want and f5["counts"][1] == again["counts"][1] == n
         for got, what in ((staged, "staged"), (f5, "f5"), (again, "again")):
-            same(got, host, (n, what))
+            U.assert_same(got, host, (n, what))
         assert f5["jobs"] == (1, 0, 0) and again["jobs"] == (1, 0, 0)
         assert staged["launches"] == 0 and host["launches"] == 0
         assert f5["launches"] == again["launches"] == int(n > w and shift > 0)
@@ -223,12 +193,7 @@ def _child(mode, form):
 
 
 def _spawn(mode, grid, waves, shift, form):
-    env = dict(os.environ, SK_F5_GRID=str(grid), SK_F5_WAVES=str(waves), SK_F5_TAIL_SHIFT=str(shift))
-    p = subprocess.run([sys.executable, os.path.abspath(__file__), mode, str(form)], env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
-                       timeout=300)
-    out = p.stdout.decode(errors="replace")
-    print(out[-3000:])
-    assert p.returncode == 0 and "TAIL-CHILD-OK" in out, out[-3000:]
+    U.spawn_child(__file__, mode, form, "TAIL-CHILD-OK", SK_F5_GRID=grid, SK_F5_WAVES=waves, SK_F5_TAIL_SHIFT=shift)
 
 
 @pytest.mark.gpu

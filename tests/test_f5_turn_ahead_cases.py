@@ -28,12 +28,11 @@ has a window of more than F5_MAX_POOL bytes and leaves F5 at the pool gate, befo
 Queue: a few distinct short reads tiled to n reads for n around the number of resident waves W (4 096 for the 152-base form, 3 072
 for the 256-base form), one of them a read the gate turns down (no candidate alignments), and sk_realign_job_rescore(2) followed by
 reading the results again.  A read whose status is not OK is not stated: the scenarios have none."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from strelka_amd import capi, synth
+from tests import f5_util as U
 
 _BASES = "ACGT"
 _CODE = {"A": 1, "C": 2, "G": 4, "T": 8, "N": 15}
@@ -179,29 +178,10 @@ def _scenarios(seed, form):
                   _crafted_walk(rng, lens[0], "rest"), _crafted_walk(rng, lens[-1], "rest")]
 
 
-def _job(sc, enumeration):
-    job = capi.RealignJob(capi.realign_options(is_haplotyping_enabled=sc["is_haplotyping_enabled"],
-                                               min_read_bp_flank=sc["min_read_bp_flank"], enumeration=enumeration))
-    job.set_reference(sc["ref_seq"], sc["ref_offset"])
-    job.set_indels(sc["indels"])
-    return job
-
-
-def _add(job, reads):
-    idx = []
-    for rd in reads:
-        try:
-            idx.append(job.add_read(rd["code"], rd["qual"], rd["pos"], rd["path"], rd["is_fwd"], rd["map_level"], 0, rd["realign_range"],
-                                    rd["observed"]))
-        except capi.StrelkaAmdError:
-            idx.append(None)
-    return idx
-
-
 def _count_cases(sc, seen, pools):
     """the cases of one job, from the host form's batch of it (no device work), its reads and its table"""
-    job = _job(sc, 0)
-    idx = _add(job, sc["reads"])
+    job = U.make_job(sc, 0)
+    idx = U.add_reads(job, sc["reads"])
     b = job.batch()
     kept = [rd for rd, i in zip(sc["reads"], idx) if i is not None]
     # (the batch holds the reads that passed the gate, in order: each is found among the job's reads by its codes)
@@ -251,22 +231,6 @@ def _count_cases(sc, seen, pools):
     seen["insert_in_no_pool"] += any(d["ins_seq"] and (d["pos"] < lo - 150 or d["pos"] > hi + 150) for d in sc["indels"])
 
 
-def _run(sc, chain, monkeypatch, reads=None, rescore=0):
-    monkeypatch.setenv("SK_A5_FUSED", "0" if chain == "staged" else "1")
-    monkeypatch.setenv("SK_ENUM_ONE_WAIT", "1")
-    before = capi.RealignJob.device_job_counts()
-    outside0 = capi.lib().sk_realign_reference_reads_outside()
-    job = _job(sc, 0 if chain == "host" else 2)
-    idx = _add(job, sc["reads"] if reads is None else reads)
-    job.run()
-    if rescore:
-        ms, nr, nc, cells = C.c_float(0), C.c_int32(0), C.c_int32(0), C.c_int64(0)
-        assert capi.lib().sk_realign_job_rescore(rescore, C.byref(ms), C.byref(nr), C.byref(nc), C.byref(cells)) == 0, capi.last_error()
-    res = [None if i is None else repr(job.result(i)) for i in idx]
-    return dict(res=res, consulted=job.indels_consulted().tolist(), outside=capi.lib().sk_realign_reference_reads_outside() - outside0,
-                counts=job.enumeration_counts(), jobs=tuple(b - a for a, b in zip(before, capi.RealignJob.device_job_counts())))
-
-
 _NEEDED = ("op_of_1", "op_of_7", "op_of_8", "op_of_9", "op_of_16", "last_op_multiple_of_8", "read_1_to_9", "lead_clip", "trail_clip",
            "penalty_before_8", "penalty_after_8", "N_in_last_8", "eq_in_last_8", "ends_at_pool_end", "seven_indels", "lead_edge",
            "trail_edge", "swap", "breakpoint_entry", "table_over_32_tab_lo", "insert_in_no_pool")
@@ -280,8 +244,8 @@ def test_f5_turn_ahead_equals_staged_and_host(seed, form, monkeypatch):
     seen = dict.fromkeys(_NEEDED, 0)
     pools, pools_all, n_f5_jobs = [], [], 0
     for sc in scs:
-        out = {chain: _run(sc, chain, monkeypatch) for chain in ("host", "staged", "f5")}
-        out["again"] = _run(sc, "f5", monkeypatch)
+        out = {chain: U.run_chain(sc, chain, setenv=monkeypatch.setenv) for chain in ("host", "staged", "f5")}
+        out["again"] = U.run_chain(sc, "f5", setenv=monkeypatch.setenv)
         f5 = out["f5"]
         print(sc["kind"], "jobs", f5["jobs"], "outside", [out[c]["outside"] for c in out], "consulted", sum(f5["consulted"]), "of",
               len(sc["indels"]))
@@ -335,7 +299,7 @@ def _queue_ref(form, monkeypatch):
     """host and staged results of the distinct reads, once per form"""
     if form not in _queue_reference:
         sc = _queue_scenario(np.random.default_rng(97400 + form), form == 256)
-        host, staged = _run(sc, "host", monkeypatch), _run(sc, "staged", monkeypatch)
+        host, staged = (U.run_chain(sc, chain, setenv=monkeypatch.setenv) for chain in ("host", "staged"))
         assert staged["res"] == host["res"] and staged["consulted"] == host["consulted"] and staged["outside"] == host["outside"] == 0
         assert all(r is not None for r in host["res"])
         n_cals = [eval(r, {"nan": float("nan"), "inf": float("inf")})["n_cals"] for r in host["res"]]
@@ -352,8 +316,8 @@ def test_f5_queue_first_read_not_drawn(form, n, monkeypatch):
     k = len(sc["reads"])
     reads = [sc["reads"][i % k] for i in range(n)]
     want = [host["res"][i % k] for i in range(n)]
-    f5 = _run(sc, "f5", monkeypatch, reads)
-    again = _run(sc, "f5", monkeypatch, reads, rescore=2)
+    f5 = U.run_chain(sc, "f5", reads, setenv=monkeypatch.setenv)
+    again = U.run_chain(sc, "f5", reads, rescore=2, setenv=monkeypatch.setenv)
     print("form", form, "reads", n, "jobs", f5["jobs"], again["jobs"], "counts", f5["counts"])
     if f5["counts"][1] > 0:   # (a job of reads the gate turns down alone has nothing for the device)
         assert f5["jobs"] == (1, 0, 0) and again["jobs"] == (1, 0, 0)
