@@ -110,6 +110,35 @@ int sk_debug_g3_global_pass_count(void);
  *  math library's double routines stand in; sk_libm_restated() then reports 0); on == 0 restores the sk_init outcome.
  *  Lets the test suite measure the documented 1e-5 bar of that path on a box where the exact path is available. */
 int sk_debug_force_device_libm(int on);
+/** Test hook: the device's evaluation of the restated libm routines (csrc/libm_flt32.h, libm_dbl64.h) and of the small scalar
+ *  functions the kernels build on them, one element per argument -- so that a test can ask "these bits in, which bits out, and by
+ *  which path" of the MI355X itself (tests/test_libm_device.py).  `fn` is one of SK_LIBM_*:
+ *    the eight raw routines (sk_libm::*_glibc): out[i] = the result, or zero bits where the routine returned false;
+ *      restated[i] = the routine's return value (1 = inside the restated domain);
+ *    what the kernels call (sk_exp .. log_sum2f), with the context's exact_libm as the kernels take it -- after
+ *      sk_debug_force_device_libm(1) the device library's stand-in is what gets evaluated; restated[i] = 0.
+ *  a, b, out are HOST arrays of n elements: float for the single-precision functions, double for the others; b only for the
+ *  two-argument functions (POWF: x, y; DEPENDENT_EPROB: eprob, vexp; LOG_SUM2, LOG_SUM2F: the two terms) and NULL otherwise;
+ *  out is int32 for the two q-score conversions.  `restated` may be NULL.
+ *  `variant` says where the exp / log tables come from: 0 = sk_libm_tables_default() (constant memory), 1 = a block's LDS copy
+ *  (sk_libm_tables_to_lds) -- for the functions that take tables: EXP, LOG, LOG10, SK_EXP, SK_LOG, SK_LOG10, QPHRED_D,
+ *  LOG1P_SWITCH_D, LOG_SUM2 --, 2 = the out-of-line twins sk_exp_call / sk_log_call / sk_log10_call (SK_EXP, SK_LOG, SK_LOG10 and
+ *  QPHRED_D, which is then the somatic callers' statement of it).  Every function takes variant 0.
+ *  Returns 0; -1 (sk_last_error) for an fn / variant pair that does not exist; 1 for any other failure.  n == 0 returns 0 and
+ *  touches nothing.  n is at most 2^24. */
+enum {
+    SK_LIBM_LOGF = 0, SK_LIBM_POWF = 1, SK_LIBM_EXPF = 2, SK_LIBM_LOG1PF = 3,
+    SK_LIBM_EXP = 4, SK_LIBM_LOG = 5, SK_LIBM_LOG10 = 6, SK_LIBM_LOG1P = 7,
+    SK_LIBM_SK_EXP = 8, SK_LIBM_SK_LOG = 9, SK_LIBM_SK_LOG10 = 10, SK_LIBM_SK_LOG1P = 11,
+    SK_LIBM_LOGF_REF = 12,        /* logf_ref (germline_common.h) */
+    SK_LIBM_DEPENDENT_EPROB = 13, /* get_dependent_eprob(a = eprob, b = vexp) */
+    SK_LIBM_LN_QPHRED_F = 14,     /* ln_error_prob_to_qphred_f, ln10f as the germline kernels' GermlineDerived has it */
+    SK_LIBM_QPHRED_D = 15,        /* error_prob_to_qphred_d */
+    SK_LIBM_LOG1P_SWITCH_D = 16, SK_LIBM_LOG_SUM2 = 17, /* log_sum.h, double */
+    SK_LIBM_LOG_SUM2F = 18,                             /* log_sum.h, float */
+    SK_LIBM_FN_COUNT = 19
+};
+int sk_debug_libm_eval(int fn, int variant, int64_t n, const void* a, const void* b, void* out, uint8_t* restated);
 /** Test hook: the bytes of device and of page-locked host memory that the library's grown buffers hold at the moment (the context's
  *  arena, every module's kept buffers, live pileup streams and callers).  Both are 0 after sk_shutdown.  Either pointer may be NULL. */
 void sk_debug_grown_bytes(int64_t* device_bytes, int64_t* pinned_bytes);

@@ -55,6 +55,11 @@ int sk_init(int) { g_ready = true; return 0; }
 int sk_init_strict(int) { g_ready = true; return 0; }
 int sk_check_device_errors(void) { return 0; }
 int sk_debug_force_device_libm(int) { return 0; }
+int sk_debug_libm_eval(int, int, int64_t, const void*, const void*, void*, uint8_t*) // (the device's evaluation: there is none here)
+{
+    g_err = "sk_debug_libm_eval: not available in the CPU double";
+    return 1;
+}
 void sk_debug_grown_bytes(int64_t* device_bytes, int64_t* pinned_bytes)
 {
     if (device_bytes) *device_bytes = 0;

@@ -113,6 +113,60 @@ def heap_sort_runs_reset():
     oracle().sko_heap_sort_runs_reset()
 
 
+# ---- the libm check: function numbers as SK_LIBM_* of include/strelka_amd.h (sko_libm_eval, strelka_oracle.h)
+LIBM_FN = {"logf": 0, "powf": 1, "expf": 2, "log1pf": 3, "exp": 4, "log": 5, "log10": 6, "log1p": 7,
+           "sk_exp": 8, "sk_log": 9, "sk_log10": 10, "sk_log1p": 11, "logf_ref": 12, "dependent_eprob": 13,
+           "ln_qphred_f": 14, "qphred_d": 15, "log1p_switch_d": 16, "log_sum2": 17, "log_sum2f": 18}
+LIBM_FLOAT_FNS = ("logf", "powf", "expf", "log1pf", "logf_ref", "dependent_eprob", "ln_qphred_f", "log_sum2f")
+LIBM_TWO_ARG_FNS = ("powf", "dependent_eprob", "log_sum2", "log_sum2f")
+LIBM_INT_OUT_FNS = ("ln_qphred_f", "qphred_d")
+HEADER_SO = os.path.join(HERE, "liblibm_header.so")
+_header = None
+
+
+def libm_in_dtype(fn):
+    return np.float32 if fn in LIBM_FLOAT_FNS else np.float64
+
+
+def libm_out_dtype(fn):
+    return np.int32 if fn in LIBM_INT_OUT_FNS else libm_in_dtype(fn)
+
+
+def libm_args(fn, a, b):
+    """(a, b) as contiguous arrays of the function's argument type; b is None exactly for the one-argument functions"""
+    t = libm_in_dtype(fn)
+    a = np.ascontiguousarray(a, t)
+    assert (b is not None) == (fn in LIBM_TWO_ARG_FNS), fn
+    if b is not None:
+        b = np.ascontiguousarray(b, t)
+        assert b.shape == a.shape
+    return a, b
+
+
+def libm_eval(fn, a, b=None):
+    """the HOST C library's result for every element (sko_libm_eval): the reference of the libm tests"""
+    a, b = libm_args(fn, a, b)
+    out = np.zeros(len(a), libm_out_dtype(fn))
+    rc = oracle().sko_libm_eval(LIBM_FN[fn], C.c_int64(len(a)), _p(a), None if b is None else _p(b), _p(out))
+    assert rc == 0, fn
+    return out
+
+
+def libm_header_eval(fn, a, b=None):
+    """(out, restated): the product's restatement headers compiled for the host (sko_libm_header_eval); the eight raw routines only"""
+    global _header
+    if _header is None:
+        if not os.path.exists(HEADER_SO):
+            build(ref=False)
+        _header = C.CDLL(HEADER_SO)
+    a, b = libm_args(fn, a, b)
+    out = np.zeros(len(a), libm_out_dtype(fn))
+    restated = np.full(len(a), 255, np.uint8)
+    rc = _header.sko_libm_header_eval(LIBM_FN[fn], C.c_int64(len(a)), _p(a), None if b is None else _p(b), _p(out), _p(restated))
+    assert rc == 0, fn
+    return out, restated
+
+
 _probe = None
 
 

@@ -433,14 +433,50 @@ double sko_score_candidate_alignment(const uint8_t* read_code, const uint8_t* re
 /* ------------------------------------------------------------------------------------ hot path B: dependent eprob */
 
 /* get_dependent_eprob (L/blt_common/adjust_joint_eprob.cpp:58-69); all blt_float_t, std::pow(float,float)=powf */
-static float get_dependent_eprob(unsigned qscore, float vexp)
+static float dependent_eprob_of(float eprob, float vexp)
 {
     static const float dep_converge_prob = 0.75f;
-    const float eprob = (float)g_q2p[qscore];
     const float val = powf(eprob, vexp);
     const float frac = (1 - val) / (1 - eprob);
     const float dep = frac * val + (1 - frac) * dep_converge_prob;
     return (eprob < dep) ? dep : eprob; /* std::max(eprob, dep) */
+}
+static float get_dependent_eprob(unsigned qscore, float vexp)
+{
+    return dependent_eprob_of((float)g_q2p[qscore], vexp);
+}
+
+/* The host libm (and the scalar restatements above) over arrays: see strelka_oracle.h.  Arguments are read through volatile
+ * pointers, so that every element is one genuine call of the C library's routine. */
+int sko_libm_eval(int fn, int64_t n, const void* a, const void* b, void* out)
+{
+    const volatile float* af = (const volatile float*)a;
+    const volatile float* bf = (const volatile float*)b;
+    const volatile double* ad = (const volatile double*)a;
+    const volatile double* bd = (const volatile double*)b;
+    float* of = (float*)out;
+    double* od = (double*)out;
+    int32_t* oi = (int32_t*)out;
+    for (int64_t i = 0; i < n; ++i) {
+        switch (fn) {
+        case 0: case 12: of[i] = logf(af[i]); break;
+        case 1: of[i] = powf(af[i], bf[i]); break;
+        case 2: of[i] = expf(af[i]); break;
+        case 3: of[i] = log1pf(af[i]); break;
+        case 4: case 8: od[i] = exp(ad[i]); break;
+        case 5: case 9: od[i] = log(ad[i]); break;
+        case 6: case 10: od[i] = log10(ad[i]); break;
+        case 7: case 11: od[i] = log1p(ad[i]); break;
+        case 13: of[i] = dependent_eprob_of(af[i], bf[i]); break;
+        case 14: oi[i] = sko_ln_error_prob_to_qphred_f(af[i]); break;
+        case 15: oi[i] = sko_error_prob_to_qphred(ad[i]); break;
+        case 16: od[i] = sko_log1p_switch(ad[i]); break;
+        case 17: od[i] = sko_log_sum2(ad[i], bd[i]); break;
+        case 18: of[i] = sko_log_sum2f(af[i], bf[i]); break;
+        default: return 1;
+        }
+    }
+    return 0;
 }
 
 /* adjust_icalls_eprob (L/blt_common/adjust_joint_eprob.cpp:92-194).  `dpc` (dependent_prob_cache) is only ever filled at

@@ -27,6 +27,18 @@ double sko_log1p_switch(double x);              /* L/blt_util/math_util.hh:33-48
 double sko_log_sum2(double a, double b);        /* L/blt_util/logSumUtil.hh:33-41 */
 float sko_log_sum2f(float a, float b);
 
+/* ---- the host C library, element by element: the expected values of the device's libm check (tests/test_libm_device.py).
+ *      fn numbers as SK_LIBM_* in include/strelka_amd.h: 0..7 logf, powf, expf, log1pf, exp, log, log10, log1p; 8..11 the same
+ *      double routines again (what sk_exp .. sk_log1p must return); 12 logf; 13 get_dependent_eprob(a = eprob, b = vexp);
+ *      14 ln_error_prob_to_qphred<float>; 15 error_prob_to_qphred<double>; 16 log1p_switch; 17 getLogSum (double); 18 (float).
+ *      a, b, out: float arrays for the single-precision functions, double otherwise; out is int32 for 14 and 15; b only for 1, 13,
+ *      17 and 18.  Never includes the product's headers.  Returns 0, or 1 for an unknown fn. */
+int sko_libm_eval(int fn, int64_t n, const void* a, const void* b, void* out);
+/* The product's restatement headers (strelka_amd/csrc/libm_flt32.h, libm_dbl64.h) compiled for the HOST, for fn 0..7: out as
+ * sko_libm_eval's, or zero bits where the routine returned false; restated[i] = its return value.  Defined in libm_header_eval.cpp
+ * (C++, oracle/liblibm_header.so). */
+int sko_libm_header_eval(int fn, int64_t n, const void* a, const void* b, void* out, uint8_t* restated);
+
 /* ---- libstdc++ std::sort restated (introsort + final insertion sort), descending-q comparator of
  *      L/blt_common/adjust_joint_eprob.cpp:41-53.  idx[n] is permuted in place; key[] is indexed by idx values. */
 void sko_sort_idx_by_key_desc(uint32_t* idx, int n, const uint16_t* key);

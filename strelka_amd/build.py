@@ -32,6 +32,8 @@ HIP_SOURCES = [
     "csrc/region_haplotypes.hip",
     "csrc/region_alleles.hip",
     "csrc/gvcf_block.hip",
+    "csrc/libm_probe.hip",
+    "csrc/libm_probe_germline.hip",
 ]
 HOST_SOURCES = [
     "host/align_flatten.cpp",

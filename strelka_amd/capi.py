@@ -229,7 +229,7 @@ assert DIGT_CALL_DTYPE.itemsize == 144 and SOMATIC_CALL_DTYPE.itemsize == 272
 
 # every symbol include/strelka_amd.h declares (tests check the library exports all of them)
 EXPORTS = [
-    "sk_device_count", "sk_host_alloc", "sk_host_free", "sk_init", "sk_init_strict", "sk_check_device_errors", "sk_debug_force_device_libm", "sk_debug_grown_bytes", "sk_debug_set_g3_variant", "sk_debug_g3_global_pass_count", "sk_shutdown", "sk_last_error", "sk_version", "sk_is_initialized", "sk_sync_mode", "sk_libm_restated", "sk_broker_client", "sk_broker_enable", "sk_broker_serve", "sk_broker_selftest", "sk_get_qscore_tables",
+    "sk_device_count", "sk_host_alloc", "sk_host_free", "sk_init", "sk_init_strict", "sk_check_device_errors", "sk_debug_force_device_libm", "sk_debug_libm_eval", "sk_debug_grown_bytes", "sk_debug_set_g3_variant", "sk_debug_g3_global_pass_count", "sk_shutdown", "sk_last_error", "sk_version", "sk_is_initialized", "sk_sync_mode", "sk_libm_restated", "sk_broker_client", "sk_broker_enable", "sk_broker_serve", "sk_broker_selftest", "sk_get_qscore_tables",
     "sk_score_alignments", "sk_score_alignments_dev", "sk_align_evmask_words", "sk_align_prepare", "sk_align_colmat_words", "sk_align_prepare_cols",
     "sk_bgzf_scan", "sk_bgzf_inflate", "sk_bgzf_inflate_prefixed", "sk_bgzf_inflate_dev", "sk_bgzf_deflate_bound", "sk_bgzf_deflate", "sk_bgzf_deflate_dev", "sk_bam_header_end", "sk_bam_scan_records", "sk_bam_decode", "sk_bam_decode_kept", "sk_bam_decode_dev", "sk_normalize_alignments", "sk_normalize_alignments_dev",
     "sk_intake_options_default", "sk_read_intake_obs_bound", "sk_read_intake", "sk_read_intake_dev", "sk_read_intake_scratch_bytes",
@@ -279,6 +279,7 @@ def lib():
         L.sk_last_error.restype = C.c_char_p
         L.sk_debug_grown_bytes.argtypes = [c_void_p, c_void_p]
         L.sk_debug_grown_bytes.restype = None
+        L.sk_debug_libm_eval.argtypes = [C.c_int, C.c_int, C.c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
         L.sk_align_builder_create.restype = c_void_p
         L.sk_align_builder_error.restype = C.c_char_p
         L.sk_align_builder_error.argtypes = [c_void_p]
@@ -487,6 +488,30 @@ def qscore_tables():
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(c_void_p)
+
+
+# SK_LIBM_* of include/strelka_amd.h
+LIBM_FN = {"logf": 0, "powf": 1, "expf": 2, "log1pf": 3, "exp": 4, "log": 5, "log10": 6, "log1p": 7,
+           "sk_exp": 8, "sk_log": 9, "sk_log10": 10, "sk_log1p": 11, "logf_ref": 12, "dependent_eprob": 13,
+           "ln_qphred_f": 14, "qphred_d": 15, "log1p_switch_d": 16, "log_sum2": 17, "log_sum2f": 18}
+_LIBM_FLOAT_FNS = ("logf", "powf", "expf", "log1pf", "logf_ref", "dependent_eprob", "ln_qphred_f", "log_sum2f")
+
+
+def debug_libm_eval(fn, a, b=None, variant=0):
+    """(out, restated): the device's evaluation of one SK_LIBM_* function (by name) on every element of a (and b)
+    (sk_debug_libm_eval); variant 0 = tables in constant memory, 1 = a block's LDS copy, 2 = the out-of-line twins"""
+    t = np.float32 if fn in _LIBM_FLOAT_FNS else np.float64
+    a = np.ascontiguousarray(a, t)
+    if b is not None:
+        b = np.ascontiguousarray(b, t)
+        assert b.shape == a.shape
+    out = np.zeros(len(a), np.int32 if fn in ("ln_qphred_f", "qphred_d") else t)
+    restated = np.full(len(a), 255, np.uint8)
+    rc = lib().sk_debug_libm_eval(LIBM_FN[fn], int(variant), len(a), _p(a), _p(b), _p(out), _p(restated))
+    if rc < 0:
+        raise ValueError(last_error())
+    _check(rc)
+    return out, restated
 
 
 # ----------------------------------------------------------------------------------------------------------------------

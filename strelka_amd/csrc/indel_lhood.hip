@@ -19,6 +19,7 @@
 // ~1e-15; indel loci are a thousandth of all loci, so the exact form is the one that ships.)
 
 #include "somatic_common.h"
+#include "log_sum.h"
 
 #include <unordered_map>
 #include <vector>
@@ -48,20 +49,7 @@ struct GridArgs
     double loghalf;
 };
 
-// log1p_switch / getLogSum, L/blt_util/math_util.hh:33-48, L/blt_util/logSumUtil.hh:33-41 (double)
-__device__ __forceinline__ double log1p_switch_d(const double x, const int ex, const SkLibmTables& lt)
-{
-    return (fabs(x) < 0.01) ? sk_log1p(x, ex) : sk_log(__dadd_rn(1., x), ex, lt);
-}
-__device__ __forceinline__ double log_sum2(double x1, double x2, const int ex, const SkLibmTables& lt)
-{
-    if (x1 < x2) {
-        const double t = x1;
-        x1 = x2;
-        x2 = t;
-    }
-    return __dadd_rn(x1, log1p_switch_d(sk_exp(__dsub_rn(x2, x1), ex, lt), ex, lt));
-}
+// (log1p_switch_d / log_sum2, the reference's log1p_switch / getLogSum in double: log_sum.h)
 
 // integrateOutMappingStatus, L/starling_common/readMappingAdjustmentUtil.hh:29-56
 __device__ __forceinline__ double integrate_out_mapping(const MapParams& m, const unsigned non_ambig, const double lnp, const int ex,

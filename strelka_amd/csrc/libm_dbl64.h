@@ -4,7 +4,10 @@
 // exp / log / log10 calls into the host C library.  glibc >= 2.28 (this image: 2.35): sysdeps/ieee754/dbl-64/e_exp.c and
 // e_log.c are the table-driven routines of ARM's optimized-routines (128-entry tables, EXP_POLY_ORDER 5, LOG_POLY_ORDER 6,
 // LOG_POLY1_ORDER 12), run in their FMA build on x86-64 CPUs with FMA; e_log10.c is the fdlibm wrapper around log, without
-// fused operations.  Restated operation for operation below; oracle/libm_check.cpp compares them with the host libm.
+// fused operations.  Restated operation for operation below; oracle/libm_check.cpp compares them with the host libm on 10^7 random
+// arguments, tests/test_libm_restatement.py on the edge sets of tests/libm_cases.py as well, and tests/test_libm_device.py compares
+// the DEVICE's evaluation (sk_debug_libm_eval: tables in constant memory, in LDS, and the out-of-line twins) with the host libm
+// bit for bit on the same sets.
 // Tables: the published constants (__exp_data, __log_data), listed with tools/libm_tables.py.
 //
 // Each function returns false outside the restated domain (the caller then uses the device library): exp for nan and
@@ -348,7 +351,8 @@ __device__ __forceinline__ double sk_log10(const double x, const int exact_libm,
 __device__ __forceinline__ double sk_log1p(const double x, const int exact_libm)
 {
     double r;
-    return (exact_libm && sk_libm::log1p_glibc(x, r)) ? r : log1p(x);
+    if (exact_libm && sk_libm::log1p_glibc(x, r)) return r;
+    return (x == 0.) ? x : log1p(x); // (the host's log1p(-0) is -0; the device library's is +0: tests/test_libm_device.py)
 }
 // Out-of-line twins for the somatic grid posterior: it unrolls ~150 call sites so that every likelihood index is static,
 // and inlining a table-driven routine into each of them makes the compiler give the unrolling up and index the

@@ -11,7 +11,9 @@
 //
 // Tables: the published constants of those routines (__powf_log2_data with POWF_SCALE_BITS = 0, __exp2f_data,
 // __logf_data), listed with tools/libm_tables.py.  tests/test_libm_restatement.py compiles this header for the host and
-// compares it with the host libm on 10^7 arguments; sk_init() repeats a short comparison and, should the host libm ever
+// compares it with the host libm on 10^7 random arguments and on the edge sets of tests/libm_cases.py; tests/test_libm_device.py
+// asks the device itself (sk_debug_libm_eval, libm_probe.hip) for each routine's bits on the same sets and requires the host
+// libm's, with no mismatch allowed; sk_init() repeats a short comparison and, should the host libm ever
 // be a different implementation, the kernels keep using the device library's double-precision pow/log instead.
 //
 // Domain: x a positive normal float, |y * log2(x)| < 126 (powf).  Anything else returns `false`: the caller falls back.

@@ -16,6 +16,7 @@
 
 #include "somatic_common.h"
 #include "libm_flt32.h"
+#include "log_sum.h"
 
 #include <cstddef>
 
@@ -43,27 +44,7 @@ __device__ __forceinline__ bool locus_is_forced(const SomArgs& a, const int l)
     return a.d.is_forced_output || a.nonsomatic || (a.forced != nullptr && a.forced[l] != 0);
 }
 
-// getLogSum<float>, L/blt_util/logSumUtil.hh:33-41 with log1p_switch<float>, L/blt_util/math_util.hh:33-48: the reference's
-// expf / log1pf / logf are the host libm's, restated for the device in libm_flt32.h; the device library's double-precision
-// functions rounded once stand in when the host libm is another implementation (sk_libm_restated() == 0)
-__device__ __forceinline__ float log_sum2f(float x1, float x2, const int exact_libm)
-{
-    if (x1 < x2) {
-        const float t = x1;
-        x1 = x2;
-        x2 = t;
-    }
-    const float d = __fsub_rn(x2, x1);
-    float e, l;
-    if (!(exact_libm && sk_libm::expf_glibc(d, e))) e = static_cast<float>(exp(static_cast<double>(d)));
-    if (fabsf(e) < 0.01f) {
-        if (!(exact_libm && sk_libm::log1pf_glibc(e, l))) l = static_cast<float>(log1p(static_cast<double>(e)));
-    } else {
-        const float one_e = __fadd_rn(1.f, e);
-        if (!(exact_libm && sk_libm::logf_glibc(one_e, l))) l = static_cast<float>(log(static_cast<double>(one_e)));
-    }
-    return __fadd_rn(x1, l);
-}
+// (log_sum2f, the strand states' getLogSum<float>: log_sum.h)
 
 // Every memoised term of one call, one LDS row per (q-score, call == reference base): 31 floats in the order the accumulators use
 // them -- ref, het, hom (is_ref ? (v2, v1, v0) : (v0, v1, v2), :56-64), the off-strand term (is_ref ? ln_comp_error_prob :
