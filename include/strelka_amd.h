@@ -1229,7 +1229,7 @@ int sk_normalize_alignments_dev(const char* dev_ref_seq, int32_t ref_offset, int
  *                 holds this sum at that moment.  Contributions outside the window are dropped.
  *
  * Out of scope: pinned edges (RNA); externally supplied candidate or forced indels (they do not come from reads); the per-read
- * haplotype store (setMatch, _positionToAlignIds, getReadSegments); the repeat finder; IndelBuffer bookkeeping.
+ * haplotype store (setMatch, _positionToAlignIds, getReadSegments); the repeat finder.  IndelBuffer bookkeeping is sk_indel_table[_dev] (below).
  * ---------------------------------------------------------------------------------------------------------------- */
 typedef struct sk_intake_options {
     uint32_t max_indel_size;        /* starling_base_options::maxIndelSize */
@@ -1459,7 +1459,7 @@ int sk_sync_region_params_dev(const sk_sync_region* dev_sync_regions, const int3
  * On one stream sk_read_intake_dev -> sk_ref_anchors_dev -> sk_active_regions_dev -> sk_region_haplotypes_dev run with no host copy
  * in between.  Out of scope: routing the results into the caller; the assembly fallback (generateHaplotypesWithAssembly,
  * getReadSegments with partial reads) -- a region whose counting fails reports its status and the host does the rest;
- * doNotUseHaplotyping's IndelBuffer marks; _haplotypesToExclude; external and forced candidates.  The multi-sample synchroniser's regions come
+ * _haplotypesToExclude; external and forced candidates (doNotUseHaplotyping's IndelBuffer marks are sk_indel_table[_dev]'s).  The multi-sample synchroniser's regions come
  * through sk_region_haplotypes_params[_dev], one call per sample.
  * What a region does with its selected haplotypes -- the aligner, the walk, the records for the buffers -- is sk_region_alleles[_dev]
  * (below), chained on the same stream without a host copy.
@@ -1563,12 +1563,12 @@ int sk_region_haplotypes_params_dev(const char* dev_ref_seq, int32_t ref_offset,
  * reference asserts, :596-599); a left shift the reference's loop would not end (an all-N indel left of an all-N reference); a
  * key whose haplotype ids add up to more than 3 (the assertion at :752); a selected haplotype longer than max_hap_len.
  * A region whose haplotype record is not SK_HAP_COUNTED, or that selected nothing, passes its status and reason through with no
- * alleles: doNotUseHaplotyping's marks and the assembly fallback stay the host's.
+ * alleles: doNotUseHaplotyping's marks are sk_indel_table[_dev]'s (below), the assembly fallback stays the host's.
  *
  * On one stream sk_read_intake_dev -> sk_ref_anchors_dev -> sk_active_regions_dev -> sk_region_haplotypes_dev ->
- * sk_region_alleles_dev run with no host copy in between.  Not routed into adapter/ yet.  Out of scope: routing;
- * addIndelObservation / addCandidateSnv themselves; the assembly fallback; doNotUseHaplotyping's marks; _haplotypesToExclude and the
- * somatic branch; filterOutConflictingForcedIndels.
+ * sk_region_alleles_dev run with no host copy in between.  Not routed into adapter/ yet.  addIndelObservation and doNotUseHaplotyping's
+ * marks over these records are sk_indel_table[_dev] (below).  Out of scope: routing; addCandidateSnv itself; the assembly fallback;
+ * _haplotypesToExclude and the somatic branch; filterOutConflictingForcedIndels.
  * ---------------------------------------------------------------------------------------------------------------- */
 enum {
     SK_ALLELE_DECLINE_BEGIN_POS = 4, /* (after SK_HAP_DECLINE_*) the aligner's beginPos > 0 */
@@ -1634,6 +1634,113 @@ int sk_region_alleles_dev(const char* dev_ref_seq, int32_t ref_offset, int32_t r
                           uint32_t max_indel_size, int32_t max_hap_len, int32_t prev_end_in, sk_region_alleles_rec* dev_recs, sk_region_allele* dev_alleles,
                           int64_t allele_cap, uint8_t* dev_insert_pool, int64_t insert_cap, int64_t* dev_totals, int32_t* dev_prev_end_out,
                           void* dev_scratch, size_t scratch_bytes, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The indel table: a window's observations merged by key -- what the reference's IndelBuffer
+ * (std::map<IndelKey, IndelData>, L/starling_common/IndelBuffer.cpp) holds after every read observation of the call has been added
+ * (addIndelObservation :95-133, IndelSampleData::addIndelObservation, IndelData.cpp:72-114) and the call's regions have then been closed
+ * in order, region by region and inside a region sample by sample (ActiveRegionDetector.cpp:204-250): a counted (region, sample) adds
+ * its records (processDiscoveredIndelsAndMismatches, ActiveRegionProcessor.cpp:709-757), a bypassed one makes doNotUseHaplotyping's marks
+ * (:265-292).  BATCH SEMANTICS: all reads first, then the regions.  Whether a window can be cut so that this equals the reference's
+ * streaming order is routing's question and stays out of scope.
+ *
+ *   rule 1  key identity and order: IndelKey::operator< (L/starling_common/IndelKey.hh:56-85) -- pos, type, then (not for breakpoints:
+ *           all breakpoint observations of one (pos, type) are one key) insert length, delete length, insert sequence in ASCII order
+ *           (A < C < G < N < T)
+ *   rule 2  every sk_intake_obs of sample s puts its read's align id into one set of (key, s): noise if is_noise, else the set iat names;
+ *           a breakpoint key counts the observation in n_bp_obs
+ *   rule 3  per sample, region and record with to_indel_buffer set: every read of hap[hap_slot]'s support list goes into the set its iat
+ *           names, never noise (:736-739); the same id twice is one member (IndelData.cpp:109-112)
+ *   rule 4  SK_ITAB_DO_NOT_GENOTYPE: a key that is neither MISMATCH nor a primitive insertion or deletion (IndelBuffer.cpp:119-128)
+ *   rule 5  the report info: getAlleleReportInfo and set_repeat_info (L/starling_common/AlleleReportInfoUtil.cpp:96-216)
+ *   rule 6  active_region_id = the region's begin; haplotype_id += id and ratio += ratio per sample in (region, record) order from 0 and
+ *           0.0f (:741-755): ordered float additions
+ *   rule 7  a (region, sample) whose haplotype record is SK_HAP_BYPASSED: every key with begin <= pos < end that is neither breakpoint nor
+ *           MISMATCH and EXISTED AT THAT STEP -- it has a read observation, or a rule 3 record of an earlier (region, sample) step -- gets
+ *           active_region_id = begin and is_haplotyping_bypassed[s] = 1.  active_region_id is the last writer's in step order.
+ *   rule 8  SK_ITAB_AR_PENDING: a (region, sample) whose haplotype record is SK_HAP_NO_READS, SK_HAP_TOO_FEW_COVERING or SK_HAP_DECLINED, or
+ *           whose alleles record declined: the reference would run the assembler, so the outcome is not known.  Such a pair writes
+ *           nothing; every key with min(begin, max(prev_end, 0)) <= pos < end gets the flag, and totals[3] counts the pairs.  Declined,
+ *           never guessed.
+ *
+ * On one stream, per sample sk_read_intake_dev ... sk_region_alleles_dev and then sk_indel_table_dev run with no host copy in between;
+ * the counts that exist only on the device stay there (dev_n_regions, obs_off[n_reads], the region records' offsets).  Out of scope:
+ * routing; the consensus of breakpointInsertionSequence (_breakpointInsertSeq); contextCompressability (only EVS reads it), the error
+ * rates and isCandidateIndel (functions of these fields plus the caller's model tables and depth buffers); carrying keys from one call to
+ * the next; external and forced candidates and filterOutConflictingForcedIndels; CandidateSnvBuffer (its records are the MISMATCH
+ * records of sk_region_alleles); the assembly fallback.
+ * ---------------------------------------------------------------------------------------------------------------- */
+enum { SK_IAT_TIER1 = 0, SK_IAT_TIER2, SK_IAT_SUBMAP }; /* INDEL_ALIGN_TYPE::GENOME_TIER1_READ, GENOME_TIER2_READ, GENOME_SUBMAP_READ */
+enum { SK_ITAB_TIER1 = 0, SK_ITAB_TIER2, SK_ITAB_SUBMAP, SK_ITAB_NOISE, SK_ITAB_N_SETS }; /* the id sets of a (key, sample) */
+enum { SK_ITAB_DO_NOT_GENOTYPE = 1, SK_ITAB_AR_PENDING = 2 }; /* sk_indel_table_key.flags */
+enum { SK_ITAB_INSERT = 0, SK_ITAB_DELETE, SK_ITAB_SWAP, SK_ITAB_BREAKPOINT, SK_ITAB_OTHER }; /* SimplifiedIndelReportType::index_t */
+typedef struct sk_indel_table_sample { /* one sample's arrays, as the chain's earlier steps took and left them (host or device memory) */
+    int32_t n_reads, pad;
+    const int64_t* read_off;     /* [n_reads + 1] */
+    const uint8_t* read_code;
+    const int64_t* obs_off;      /* [n_reads + 1] as sk_read_intake leaves it */
+    const sk_intake_obs* obs;
+    int64_t obs_cap;             /* the room of obs */
+    const uint32_t* align_id;    /* [n_reads] the caller's align_id_t; NULL: the read's index */
+    const uint8_t* iat;          /* [n_reads] SK_IAT_*: alignInfo.indelAlignType */
+    const sk_region_haplotypes_rec* hap_recs; /* [n_regions] over the SHARED region list */
+    const int32_t* support_pool;
+    int64_t support_cap;         /* the room of support_pool */
+    const sk_region_alleles_rec* recs; /* [n_regions] */
+    const sk_region_allele* alleles;
+    int64_t allele_cap;          /* the room of alleles */
+    const uint8_t* insert_pool;
+    int64_t insert_cap;          /* the room of insert_pool */
+} sk_indel_table_sample;
+typedef struct sk_indel_table_key {
+    int32_t pos, type;           /* key.pos; SK_INDEL_* */
+    uint32_t del_len, ins_len;   /* key.deletionLength; key.insertSequence is insert_pool[ins_off .. ins_off + ins_len) of the TABLE's pool */
+    int64_t ins_off;
+    int32_t active_region_id;    /* IndelData::activeRegionId; -1 when never set */
+    uint32_t flags;              /* SK_ITAB_DO_NOT_GENOTYPE | SK_ITAB_AR_PENDING */
+    uint32_t n_bp_obs;           /* breakpoint keys: the observations counted (rule 2) */
+    int32_t it;                  /* AlleleReportInfo::it, SK_ITAB_INSERT .. SK_ITAB_OTHER */
+    uint32_t repeat_unit_len, ref_repeat_count, indel_repeat_count, interrupted_hpol_len;
+} sk_indel_table_key;
+typedef struct sk_indel_table_sample_data { /* IndelSampleData of (key, sample): data[key * n_samples + sample] */
+    int64_t off[SK_ITAB_N_SETS];    /* the set's ids: id_pool[off .. off + count), ascending and unique, as std::set<align_id_t> iterates */
+    uint32_t count[SK_ITAB_N_SETS];
+    int32_t haplotype_id;
+    uint32_t is_haplotyping_bypassed;
+    float ratio;                 /* altAlleleHaplotypeCountRatio */
+    uint32_t pad;
+} sk_indel_table_sample_data;
+/** Room for the keys: every observation and every allele record could be a key of its own.  Host arithmetic only (works without a
+ *  device); -1 for a negative count. */
+int64_t sk_indel_table_key_bound(int64_t n_obs_total, int64_t n_allele_records_total);
+/** Room for the ids: one per observation and one per (allele record, supporting read).  Host arithmetic only; -1 for a negative count. */
+int64_t sk_indel_table_id_bound(int64_t n_obs_total, int64_t n_expanded_support_total);
+/** Room for the keys' insert bytes: an observation's insert is a range of its read's bases and a record's lies in its sample's insert pool,
+ *  so the reads' bases plus the pools' bytes.  Host arithmetic only; -1 for a negative count. */
+int64_t sk_indel_table_insert_bound(int64_t n_read_bases_total, int64_t n_allele_insert_bytes_total);
+/** Bytes of device scratch sk_indel_table_dev needs for expand_cap expanded records (one per observation, one per allele record with
+ *  to_indel_buffer set and one per supporting read of such a record) over region_cap regions.  Host arithmetic only; 0 for arguments out
+ *  of range. */
+size_t sk_indel_table_scratch_bytes(int32_t n_samples, int64_t expand_cap, int64_t region_cap);
+/** samples[n_samples], n_samples in 1..SK_MAX_SAMPLES; regions[n_regions] the shared list every sample's hap_recs / recs were made over,
+ *  prev_end_in as sk_region_alleles took it.  keys[0 .. totals[0]) in IndelKey::operator< order, data[totals[0] * n_samples], id_pool
+ *  (totals[1] ids), insert_pool (totals[2] bytes), totals[4]: keys, ids, insert bytes, pending (region, sample) pairs.  All struct padding
+ *  is zero.  A to_indel_buffer record whose haplotype has no supporting read still makes its key (the reference asserts there, :742).
+ *  Refused with a message: n_samples outside 1..SK_MAX_SAMPLES, an iat above 2, obs_off or read_off not beginning at 0 or descending, an
+ *  observation outside its read or a record outside its pools, key_cap / id_cap / insert_cap below the bounds of what the arrays hold,
+ *  negative sizes.  The records of one sample may lie in any order of allele_off: rule 6 adds in (region, record) order. */
+int sk_indel_table(int32_t n_samples, const sk_indel_table_sample* samples, const char* ref_seq, int32_t ref_offset, int32_t ref_len,
+                   const sk_active_region* regions, int32_t n_regions, int32_t prev_end_in, sk_indel_table_key* keys, int64_t key_cap,
+                   sk_indel_table_sample_data* data, uint32_t* id_pool, int64_t id_cap, uint8_t* insert_pool, int64_t insert_cap, int64_t* totals);
+/** The same on device memory: samples is a HOST array whose pointers are device memory; dev_regions / dev_n_regions as the chain leaves
+ *  them (region_cap: the room of dev_regions and of every sample's hap_recs and recs); dev_data has room for key_cap * n_samples records;
+ *  only enqueues.  Input the host entry would refuse, or expand_cap / key_cap / id_cap / insert_cap below what the arrays turn out to hold,
+ *  raises the sticky device flag (sk_check_device_errors) and leaves an empty table: totals all 0.  One thing the device form cannot test:
+ *  the sample record carries no room of read_code, so read_off[n_reads] is taken as the caller gives it (as the chain's earlier steps do). */
+int sk_indel_table_dev(int32_t n_samples, const sk_indel_table_sample* samples, const char* dev_ref_seq, int32_t ref_offset, int32_t ref_len,
+                       const sk_active_region* dev_regions, const int32_t* dev_n_regions, int64_t region_cap, int32_t prev_end_in, int64_t expand_cap,
+                       sk_indel_table_key* dev_keys, int64_t key_cap, sk_indel_table_sample_data* dev_data, uint32_t* dev_id_pool, int64_t id_cap,
+                       uint8_t* dev_insert_pool, int64_t insert_cap, int64_t* dev_totals, void* dev_scratch, size_t scratch_bytes, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * SURVEY.md section 8f rank 4, the output side: the non-variant blocks of the gVCF.

@@ -31,6 +31,7 @@ HIP_SOURCES = [
     "csrc/active_region_detect.hip",
     "csrc/region_haplotypes.hip",
     "csrc/region_alleles.hip",
+    "csrc/indel_table.hip",
     "csrc/gvcf_block.hip",
     "csrc/libm_probe.hip",
     "csrc/libm_probe_germline.hip",

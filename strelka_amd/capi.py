@@ -238,6 +238,7 @@ EXPORTS = [
     "sk_region_haplotypes_params", "sk_region_haplotypes_params_dev",
     "sk_region_haplotypes_seq_bound", "sk_region_haplotypes_support_bound", "sk_region_haplotypes_scratch_bytes", "sk_region_haplotypes", "sk_region_haplotypes_dev",
     "sk_region_alleles_allele_bound", "sk_region_alleles_insert_bound", "sk_region_alleles_scratch_bytes", "sk_region_alleles", "sk_region_alleles_dev", "sk_debug_region_alleles",
+    "sk_indel_table_key_bound", "sk_indel_table_id_bound", "sk_indel_table_insert_bound", "sk_indel_table_scratch_bytes", "sk_indel_table", "sk_indel_table_dev",
     "sk_align_builder_create", "sk_align_builder_destroy", "sk_align_builder_clear", "sk_align_builder_append", "sk_align_builder_add_read",
     "sk_align_builder_finish", "sk_align_builder_error", "sk_align_builder_set_host_threads",
     "sk_align_scores_default", "sk_global_align",
@@ -402,6 +403,15 @@ def lib():
                                         c_void_p, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, c_void_p]
         L.sk_region_alleles_dev.argtypes = [c_void_p, C.c_int32, C.c_int32, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p, C.c_int64, C.c_uint32, C.c_int32,
                                             C.c_int32, c_void_p, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, c_void_p, c_void_p, C.c_size_t, c_void_p]
+        for f in (L.sk_indel_table_key_bound, L.sk_indel_table_id_bound, L.sk_indel_table_insert_bound):
+            f.restype = C.c_int64
+            f.argtypes = [C.c_int64, C.c_int64]
+        L.sk_indel_table_scratch_bytes.restype = C.c_size_t
+        L.sk_indel_table_scratch_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int64]
+        L.sk_indel_table.argtypes = [C.c_int32, c_void_p, c_void_p, C.c_int32, C.c_int32, c_void_p, C.c_int32, C.c_int32, c_void_p, C.c_int64, c_void_p, c_void_p, C.c_int64,
+                                     c_void_p, C.c_int64, c_void_p]
+        L.sk_indel_table_dev.argtypes = [C.c_int32, c_void_p, c_void_p, C.c_int32, C.c_int32, c_void_p, c_void_p, C.c_int64, C.c_int32, C.c_int64, c_void_p, C.c_int64,
+                                         c_void_p, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, c_void_p, C.c_size_t, c_void_p]
         L.sk_align_colmat_words.restype = C.c_int64
         L.sk_align_colmat_words.argtypes = [c_void_p]
         L.sk_align_prepare_cols.argtypes = [c_void_p] * 4
@@ -1886,6 +1896,104 @@ def region_alleles(ref_seq, ref_offset, regions, haplotypes, max_indel_size=49, 
                                _p(totals), _p(prev_end_out)))
     res = dict(recs=recs[:m], alleles=alleles[:int(totals[0])], insert_pool=insert_pool[:int(totals[1])], totals=totals, prev_end_out=int(prev_end_out[0]))
     return res if raw else (region_allele_records(res["recs"], res["alleles"], res["insert_pool"]), res["prev_end_out"])
+
+
+IAT_TIER1, IAT_TIER2, IAT_SUBMAP = range(3)
+ITAB_TIER1, ITAB_TIER2, ITAB_SUBMAP, ITAB_NOISE, ITAB_N_SETS = range(5)
+ITAB_DO_NOT_GENOTYPE, ITAB_AR_PENDING = 1, 2
+INDEL_TABLE_KEY_DTYPE = np.dtype([("pos", "<i4"), ("type", "<i4"), ("del_len", "<u4"), ("ins_len", "<u4"), ("ins_off", "<i8"), ("active_region_id", "<i4"), ("flags", "<u4"),
+                                  ("n_bp_obs", "<u4"), ("it", "<i4"), ("repeat_unit_len", "<u4"), ("ref_repeat_count", "<u4"), ("indel_repeat_count", "<u4"),
+                                  ("interrupted_hpol_len", "<u4")])
+INDEL_TABLE_SAMPLE_DATA_DTYPE = np.dtype([("off", "<i8", (ITAB_N_SETS,)), ("count", "<u4", (ITAB_N_SETS,)), ("haplotype_id", "<i4"), ("is_haplotyping_bypassed", "<u4"),
+                                          ("ratio", "<f4"), ("pad", "<u4")])
+assert INDEL_TABLE_KEY_DTYPE.itemsize == 56 and INDEL_TABLE_SAMPLE_DATA_DTYPE.itemsize == 64
+
+
+class IndelTableSample(C.Structure):  # sk_indel_table_sample
+    _fields_ = [("n_reads", C.c_int32), ("pad", C.c_int32), ("read_off", c_void_p), ("read_code", c_void_p), ("obs_off", c_void_p), ("obs", c_void_p), ("obs_cap", C.c_int64),
+                ("align_id", c_void_p), ("iat", c_void_p), ("hap_recs", c_void_p), ("support_pool", c_void_p), ("support_cap", C.c_int64), ("recs", c_void_p),
+                ("alleles", c_void_p), ("allele_cap", C.c_int64), ("insert_pool", c_void_p), ("insert_cap", C.c_int64)]
+
+
+def indel_table_bounds(n_obs_total, n_allele_records_total, n_expanded_support_total, n_read_bases_total, n_allele_insert_bytes_total):
+    """room for the keys, the ids and the insert bytes; host arithmetic, works without a device"""
+    L = lib()
+    return (int(L.sk_indel_table_key_bound(int(n_obs_total), int(n_allele_records_total))), int(L.sk_indel_table_id_bound(int(n_obs_total), int(n_expanded_support_total))),
+            int(L.sk_indel_table_insert_bound(int(n_read_bases_total), int(n_allele_insert_bytes_total))))
+
+
+def indel_table_records(keys, data, id_pool, insert_pool, n_samples):
+    """INDEL_TABLE_KEY_DTYPE[], INDEL_TABLE_SAMPLE_DATA_DTYPE[n_keys * n_samples] and the two pools -> [dict(pos, type, del_len, ins, active_region_id,
+    flags, n_bp_obs, it, repeat_unit_len, ref_repeat_count, indel_repeat_count, interrupted_hpol_len, samples [dict(ids [[tier1], [tier2],
+    [submap], [noise]], haplotype_id, is_haplotyping_bypassed, ratio)])]: the table as plain records; floats as their bits"""
+    out = []
+    for k, key in enumerate(keys):
+        io, il = int(key["ins_off"]), int(key["ins_len"])
+        rec = dict(pos=int(key["pos"]), type=int(key["type"]), del_len=int(key["del_len"]), ins=bytes(insert_pool[io:io + il]).decode("latin-1"))
+        for f in ("active_region_id", "flags", "n_bp_obs", "it", "repeat_unit_len", "ref_repeat_count", "indel_repeat_count", "interrupted_hpol_len"):
+            rec[f] = int(key[f])
+        rec["samples"] = []
+        for d in data[k * n_samples:(k + 1) * n_samples]:
+            ids = [[int(x) for x in id_pool[int(d["off"][c]):int(d["off"][c]) + int(d["count"][c])]] for c in range(ITAB_N_SETS)]
+            rec["samples"].append(dict(ids=ids, haplotype_id=int(d["haplotype_id"]), is_haplotyping_bypassed=int(d["is_haplotyping_bypassed"]), ratio=float_bits(d["ratio"])))
+        out.append(rec)
+    return out
+
+
+def pack_indel_table_sample(sample, n_regions):
+    """dict(reads, intake (read_intake's result), align_id (or None), iat, haplotypes (region_haplotypes(..., raw=True)), alleles
+    (region_alleles(..., raw=True))) -> (IndelTableSample, the arrays it points into, dict of the sizes the bounds take)"""
+    n = len(sample["reads"])
+    read_off, code, _, _, _, _ = pack_reads(sample["reads"])
+    keep = dict(read_off=read_off, code=code, obs_off=np.ascontiguousarray(sample["intake"]["obs_off"], np.int64),
+                obs=np.ascontiguousarray(sample["intake"]["obs"], INTAKE_OBS_DTYPE),
+                align_id=None if sample.get("align_id") is None else np.ascontiguousarray(list(sample["align_id"]) + [0], np.uint32),
+                iat=np.ascontiguousarray(list(sample["iat"]) + [0], np.uint8), hap=np.ascontiguousarray(sample["haplotypes"]["recs"], REGION_HAPLOTYPES_DTYPE),
+                support=np.ascontiguousarray(sample["haplotypes"]["support_pool"], np.int32), recs=np.ascontiguousarray(sample["alleles"]["recs"], REGION_ALLELES_DTYPE),
+                alleles=np.ascontiguousarray(sample["alleles"]["alleles"], REGION_ALLELE_DTYPE), ins=np.ascontiguousarray(sample["alleles"]["insert_pool"], np.uint8))
+    assert len(keep["hap"]) == n_regions and len(keep["recs"]) == n_regions
+    ptr = lambda x: None if x is None or len(x) == 0 else x.ctypes.data
+    st = IndelTableSample(n, 0, ptr(read_off), ptr(code), ptr(keep["obs_off"]), ptr(keep["obs"]), len(keep["obs"]), ptr(keep["align_id"]), ptr(keep["iat"]), ptr(keep["hap"]),
+                          ptr(keep["support"]), len(keep["support"]), ptr(keep["recs"]), ptr(keep["alleles"]), len(keep["alleles"]), ptr(keep["ins"]), len(keep["ins"]))
+    n_support = 0
+    for i in range(n_regions):
+        h, r = keep["hap"][i], keep["recs"][i]
+        for a in keep["alleles"][int(r["allele_off"]):int(r["allele_off"]) + int(r["n_alleles"])]:
+            if int(a["to_indel_buffer"]) and 0 <= int(a["hap_slot"]) < HAP_MAX_SELECTED:
+                n_support += int(h["hap"][int(a["hap_slot"])]["count"])
+    sizes = dict(n_obs=len(keep["obs"]), n_alleles=len(keep["alleles"]), n_support=n_support, n_bases=int(read_off[-1]), n_ins=len(keep["ins"]))
+    return st, keep, sizes
+
+
+def indel_table(ref_seq, ref_offset, samples, regions, prev_end_in=-1, raw=False, caps=None):
+    """samples: [the dicts pack_indel_table_sample takes], at most MAX_SAMPLES; regions: the shared list, ACTIVE_REGION_DTYPE[] or [(begin, end)]
+    -> (the table as plain records (indel_table_records), totals [keys, ids, insert bytes, pending pairs]) through sk_indel_table;
+    raw=True: dict(keys, data, id_pool, insert_pool, totals) as the entry point leaves them.  caps: (key_cap, id_cap, insert_cap) instead of
+    the bounds"""
+    L = lib()
+    if isinstance(regions, np.ndarray) and regions.dtype == ACTIVE_REGION_DTYPE:
+        reg = np.ascontiguousarray(regions)
+    else:
+        reg = np.zeros(len(regions), ACTIVE_REGION_DTYPE)
+        for i, r in enumerate(regions):
+            reg[i] = (int(r[0]), int(r[1]), 0)
+    m = len(reg)
+    packed = [pack_indel_table_sample(s, m) for s in samples]
+    arr = (IndelTableSample * max(len(packed), 1))(*[p[0] for p in packed])
+    tot = {k: sum(p[2][k] for p in packed) for k in ("n_obs", "n_alleles", "n_support", "n_bases", "n_ins")}
+    key_cap, id_cap, insert_cap = caps or indel_table_bounds(tot["n_obs"], tot["n_alleles"], tot["n_support"], tot["n_bases"], tot["n_ins"])
+    n_samples = len(packed)
+    keys = np.zeros(max(key_cap, 1), INDEL_TABLE_KEY_DTYPE)
+    data = np.zeros(max(key_cap, 1) * max(n_samples, 1), INDEL_TABLE_SAMPLE_DATA_DTYPE)
+    id_pool = np.zeros(max(id_cap, 1), np.uint32)
+    insert_pool = np.zeros(max(insert_cap, 1), np.uint8)
+    totals = np.zeros(4, np.int64)
+    ref_b = ref_seq.encode() if isinstance(ref_seq, str) else bytes(ref_seq)
+    _check(L.sk_indel_table(n_samples, C.addressof(arr), ref_b, int(ref_offset), len(ref_b), _p(reg) if m else None, m, int(prev_end_in), _p(keys), key_cap, _p(data),
+                            _p(id_pool), id_cap, _p(insert_pool), insert_cap, _p(totals)))
+    nk = int(totals[0])
+    res = dict(keys=keys[:nk], data=data[:nk * n_samples], id_pool=id_pool[:int(totals[1])], insert_pool=insert_pool[:int(totals[2])], totals=totals)
+    return res if raw else (indel_table_records(res["keys"], res["data"], res["id_pool"], res["insert_pool"], n_samples), [int(x) for x in totals])
 
 
 BAI_CHUNK_DTYPE = np.dtype([("begin", "<u8"), ("end", "<u8")])

@@ -5,6 +5,8 @@
 
 #include "sk_common.h"
 
+#include "block_scan.h"
+
 #include <climits>
 
 namespace
@@ -59,27 +61,6 @@ __global__ __launch_bounds__(256) void copy_segments_kernel(const CopyArgs a)
     } else {
         for (int64_t i = tid; i < s.bytes; i += stride) s.dst[i] = s.src[i];
     }
-}
-
-// a block's inclusive scan of one value per thread (1 024 threads), `op` associative; `carry` joins from the chunk before
-template <typename T, typename OP>
-__device__ __forceinline__ T block_scan_1024(T v, const OP op, T* s_wave /*[16]*/)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const T up = __shfl_up(v, d, 64);
-        if (lane >= d) v = op(up, v);
-    }
-    if (lane == 63) s_wave[wave] = v;
-    __syncthreads();
-    if (wave > 0) {
-        T pre = s_wave[0];
-        for (int w = 1; w < wave; ++w) pre = op(pre, s_wave[w]);
-        v = op(pre, v);
-    }
-    __syncthreads();
-    return v;
 }
 
 // block 0: maxend[i] = max of the spans' ends up to read i; block 1: minbegin[i] = min of the spans' begins from read i on

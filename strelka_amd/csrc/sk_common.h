@@ -117,7 +117,8 @@ enum {
     SK_DEVERR_ACTIVE_REGION = 4u, // sk_active_regions_dev: createActiveRegion's assertion failed; sk_ref_anchors_dev: a span_pos before m
     SK_DEVERR_HAPLOTYPES = 8u, // sk_region_haplotypes_dev met a read or a region its host entry refuses, or ran out of a pool
     SK_DEVERR_ALLELES = 16u, // sk_region_alleles_dev met a haplotype record its host entry refuses, or a capacity below its bound
-    SK_DEVERR_SYNC_REGIONS = 32u // sk_sync_active_regions_dev: createActiveRegion's or closeActiveRegion's assertion failed, or marks its host entry refuses
+    SK_DEVERR_SYNC_REGIONS = 32u, // sk_sync_active_regions_dev: createActiveRegion's or closeActiveRegion's assertion failed, or marks its host entry refuses
+    SK_DEVERR_INDEL_TABLE = 64u // sk_indel_table_dev met input its host entry refuses, or a capacity below what the arrays hold
 };
 
 SkContext& sk_ctx();

@@ -394,6 +394,8 @@ int sk_check_device_errors(void)
         return sk_fail("sk_region_alleles_dev: a haplotype record outside the sequence pool or with more than two alternates, a counted region of no or more than 250 positions, or a capacity below its bound");
     if (flags & SK_DEVERR_SYNC_REGIONS)
         return sk_fail("sk_sync_active_regions_dev: a region's start is not before its end anchor (createActiveRegion's assertion), a synchronised region of no positions (closeActiveRegion's assertion), ploidy marks not ascending or other than 1 or 2, or region_cap too small");
+    if (flags & SK_DEVERR_INDEL_TABLE)
+        return sk_fail("sk_indel_table_dev: an iat above 2, an observation outside its read, a record or support list outside its pools, or a capacity below what the arrays hold");
     return sk_fail("strelka_amd: a kernel reported an error");
 }
 
