@@ -1743,6 +1743,131 @@ int sk_indel_table_dev(int32_t n_samples, const sk_indel_table_sample* samples, 
                        uint8_t* dev_insert_pool, int64_t insert_cap, int64_t* dev_totals, void* dev_scratch, size_t scratch_bytes, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Indel candidacy: what the reference derives from an IndelBuffer entry before anything downstream reads
+ * it -- the four error rates IndelSampleData::initializeAuxInfo stores per (key, sample) (L/starling_common/IndelData.cpp:135-160) and
+ * isCandidateIndel (isCandidateIndelImplTest and its two helpers, L/starling_common/IndelBuffer.cpp:137-263) -- and the two depth
+ * buffers per sample the latter reads (estdepth_buff, estdepth_buff_tier2).
+ *
+ *   rule D  the depth buffers: add_alignment_to_depth_buffer (L/blt_util/depth_buffer_util.cpp:30-48) over a sample's reads by map level
+ *           as load_read_in_depth_buffer does (L/starling_common/starling_pos_processor_base.cpp:626-644): every alignment-match segment
+ *           (MATCH, SEQ_MATCH, SEQ_MISMATCH) adds 1 to each reference position it covers, DELETE and SKIP advance the position without
+ *           counting, every other type does neither; SK_IAT_TIER1 reads count in depth1, SK_IAT_TIER2 reads in depth2, SK_IAT_SUBMAP reads
+ *           in neither.  Contributions outside [win_begin, win_begin + n_pos) are dropped; a position nobody covers reads 0
+ *           (depth_buffer::val of an absent key).  +1 / -1 at the segment ends with integer atomics, then a scan: deterministic.
+ *   rule E  the rates: IndelErrorModel::getIndelErrorRate (L/calibration/IndelErrorModel.cpp:226-274) with getRateType and
+ *           IndelErrorRateSet::getRate (L/calibration/IndelErrorRateSet.hh:43-60, :82-110: the clamps, and the revert to (1, 1) when the
+ *           pattern size is not represented), once on the sample's set (or the shared one) and once on the candidate set; the first
+ *           pair's indelToRefErrorProb then goes through scaleIndelErrorRate (L/starling_common/IndelData.cpp:118-131: min(rate, 0.5),
+ *           softMaxInverseTransform, + log_indel_ref_error_factor, softMaxTransform, L/blt_util/prob_util.hh:45-103) when
+ *           is_indel_ref_error_factor is set.  The candidate pair is never scaled.  Doubles, bit for bit: log and exp are the restated
+ *           ones of csrc/libm_dbl64.h when the host libm is the one restated (sk_libm_restated).
+ *   rule B  the breakpoint insert size: BreakpointInsertSequenceManager::getSize over what addObservation kept
+ *           (L/starling_common/IndelData.hh:147-160, :163-192): the longest bp_len among the observations of the key's (pos, type) over
+ *           all samples.  addObservation ignores observations after the 257th, so with n_bp_obs > 257 the size depends on the arrival
+ *           order, which a batch does not have: bp_insert_size is then the maximum over ALL observations, an upper bound (rule C4).
+ *   rule C  isCandidateIndelImplTest, in its order:
+ *           C1  SK_ITAB_DO_NOT_GENOTYPE: not a candidate (:218).  In the reference every breakpoint key carries it (IndelBuffer.cpp:119-128).
+ *           C2  is_haplotyping_enabled and active_region_id < 0: not a candidate (:221)
+ *           C3  the signal test (:137-189), sample by sample: n1 = count[SK_ITAB_TIER1], total = max(depth1[pos - 1], n1) (0 outside the
+ *               window); total < 2 skips the sample; else min_count_binom_gte_cache::isRejectNull(total, candidate_indel_to_ref, n1)
+ *               (L/starling_common/min_count_binom_gte_cache.cpp:127-153): p <= 0 gives n1 > 0; n1 == 0 gives false; when p / (1 - p) <=
+ *               0.01 and total * p < papprox[17], total * p < papprox[min(n1, 18) - 1].  The first sample that says true ends the loop.
+ *               Anything else is the exact binomial quantile (min_count_binomial_gte_exact), which is NOT built: the key is
+ *               SK_ICAND_EXACT_BINOMIAL.  With is_candidate_indel_signal_test off: any sample with n1 >= 1 (:193-208).
+ *           C4  a breakpoint key with min_candidate_indel_open_length > bp_insert_size: not a candidate (:237-241).  With n_bp_obs > 257
+ *               this holds for certain when the upper bound is below the length; otherwise the key is SK_ICAND_BP_OBS_ORDER.
+ *           C5  max_candidate_depth > 0: the sum, as a double in sample order, of depth1[pos - 1] + depth2[pos - 1] over the samples with
+ *               is_count_towards_depth_filter set; a sum above the limit: not a candidate (:246-260)
+ *           A key flagged SK_ITAB_AR_PENDING that passed C1 is SK_ICAND_AR_PENDING: its region's outcome, hence its read sets and its
+ *           region id, are not known.  Declined, never guessed: an undecided key has is_candidate == 0 and the caller asks the reference.
+ *
+ * BATCH SEMANTICS: all of the call's reads are in the depth arrays before any key is judged.  The reference evaluates candidacy lazily,
+ * at the first question about a key, and caches the answer; whether the two coincide at a window cut is routing's question.
+ * On one stream sk_indel_table_dev -> sk_read_depth_dev (per sample) -> sk_indel_candidates_dev run with no host copy; the key count
+ * stays on the device.  Out of scope: routing; external and forced candidates and notDiscoveredFromReads, which only they set
+ * (isCandidateIndelImpl :275-290); the breakpoint consensus sequence; the exact binomial fallback; papprox itself (the reference computes
+ * it once per process from alpha with boost's gamma_p_inv: caller data here); anything in adapter/.
+ * ---------------------------------------------------------------------------------------------------------------- */
+enum { SK_RATE_MAX_SIZES = 4, SK_RATE_MAX_COUNTS = 40, SK_ICAND_PAPPROX = 18, SK_ICAND_MAX_BP_OBS = 257 };
+/* IndelErrorRateSet::maxRepeatingPatternSize, maxPatternRepeatCount (IndelErrorRateSet.hh:168-169); min_count_binom_gte_cache::_maxCacheK;
+ * the observations BreakpointInsertSequenceManager::addObservation takes (IndelData.hh:179-180) */
+enum { SK_ICAND_DECIDED = 0, SK_ICAND_AR_PENDING, SK_ICAND_EXACT_BINOMIAL, SK_ICAND_BP_OBS_ORDER }; /* sk_indel_candidate.undecided */
+typedef struct sk_indel_rate_set { /* IndelErrorRateSet::_errorRates, jagged: rates of pattern size i + 1 for repeat counts 1..n_counts[i] */
+    uint32_t n_sizes;                       /* 1..SK_RATE_MAX_SIZES */
+    uint32_t n_counts[SK_RATE_MAX_SIZES];   /* 1..SK_RATE_MAX_COUNTS for i < n_sizes */
+    uint32_t pad[3];
+    double insertion[SK_RATE_MAX_SIZES][SK_RATE_MAX_COUNTS]; /* insertionErrorRate, in [0, 1] */
+    double deletion[SK_RATE_MAX_SIZES][SK_RATE_MAX_COUNTS];  /* deletionErrorRate */
+} sk_indel_rate_set;
+typedef struct sk_indel_candidate_options {
+    double papprox[SK_ICAND_PAPPROX];         /* min_count_binom_gte_cache::_papprox: strictly ascending */
+    double log_indel_ref_error_factor;        /* starling_base_deriv_options::logIndelRefErrorFactor = std::log(indelRefErrorFactor) */
+    double max_candidate_depth;               /* IndelBuffer::_maxCandidateDepth; <= 0: no depth filter */
+    uint32_t min_candidate_indel_open_length; /* starling_base_options::min_candidate_indel_open_length */
+    uint8_t is_indel_ref_error_factor;        /* isIndelRefErrorFactor */
+    uint8_t is_haplotyping_enabled;           /* isHaplotypingEnabled */
+    uint8_t is_candidate_indel_signal_test;   /* is_candidate_indel_signal_test */
+    uint8_t is_sample_specific_rates;         /* IndelErrorModel::_isUseSampleSpecificErrorRates: rate_sets holds one set per sample */
+    uint8_t is_count_towards_depth_filter[SK_MAX_SAMPLES]; /* IndelBuffer::registerSample's third argument, per sample */
+} sk_indel_candidate_options;
+/** The reference's defaults (L/starling_common/starling_base_shared.hh:98, :129, :137, :157, :237-238; IndelBuffer.hh:286): signal test on,
+ *  open length 20, no error factor (log factor 0.0), haplotyping off, no depth filter (-1.0), shared rates, every sample counted.  papprox
+ *  is left zero: the reference computes it once per process (gamma_p_inv(k, alpha), alpha = 1e-9), the caller copies it from there, and
+ *  the entries refuse it until then. */
+void sk_indel_candidate_options_default(sk_indel_candidate_options* o);
+typedef struct sk_indel_candidate_sample { /* one sample's arrays (host or device memory) */
+    int32_t n_reads, pad;
+    const int64_t* obs_off;      /* [n_reads + 1] as sk_read_intake leaves it; only obs_off[n_reads] is read */
+    const sk_intake_obs* obs;    /* the observations the table was made of: rule B reads type, pos, bp_len */
+    int64_t obs_cap;             /* the room of obs */
+    const uint32_t* depth1;      /* [n_pos] as sk_read_depth leaves them */
+    const uint32_t* depth2;
+} sk_indel_candidate_sample;
+typedef struct sk_indel_candidate { /* per key */
+    uint8_t is_candidate;        /* 0 or 1; 0 when undecided */
+    uint8_t undecided;           /* SK_ICAND_*: 0 when decided */
+    uint16_t pad;
+    uint32_t bp_insert_size;     /* getBreakpointInsertSize(); 0 for a key that is no breakpoint */
+} sk_indel_candidate;
+typedef struct sk_indel_error_rates { /* IndelErrorRates of (key, sample): rates[key * n_samples + sample] */
+    double ref_to_indel, indel_to_ref, candidate_ref_to_indel, candidate_indel_to_ref;
+} sk_indel_error_rates;
+/** Bytes of device scratch sk_read_depth_dev needs.  Host arithmetic only; 0 for a negative n_pos. */
+size_t sk_read_depth_scratch_bytes(int32_t n_pos);
+/** Rule D for one sample: the reads' alignments as sk_read_intake takes them (pos, path_off, n_seg, path; path_cap: the room of path) and
+ *  iat[n_reads] as sk_indel_table takes it; depth1[n_pos], depth2[n_pos].  The reference's functions have no option, so there is no
+ *  options record.  Refused with a message: an iat above 2, path_off[r] + n_seg[r] outside path_cap or a negative n_seg, a segment type
+ *  above SK_SEG_SEQ_MISMATCH, negative sizes. */
+int sk_read_depth(int32_t n_reads, const int64_t* path_off, const int32_t* n_seg, const sk_path_seg* path, int64_t path_cap, const int32_t* pos,
+                  const uint8_t* iat, int32_t win_begin, int32_t n_pos, uint32_t* depth1, uint32_t* depth2);
+/** The same on device memory; only enqueues.  Input the host entry would refuse raises the sticky device flag (sk_check_device_errors)
+ *  and leaves both arrays zero. */
+int sk_read_depth_dev(int32_t n_reads, const int64_t* dev_path_off, const int32_t* dev_n_seg, const sk_path_seg* dev_path, int64_t path_cap,
+                      const int32_t* dev_pos, const uint8_t* dev_iat, int32_t win_begin, int32_t n_pos, uint32_t* dev_depth1, uint32_t* dev_depth2,
+                      void* dev_scratch, size_t scratch_bytes, void* hip_stream);
+/** Bytes of device scratch sk_indel_candidates_dev needs.  Host arithmetic only. */
+size_t sk_indel_candidates_scratch_bytes(void);
+/** Rules E, B and C over keys[n_keys] / data[n_keys * n_samples] as sk_indel_table leaves them.  samples[n_samples], n_samples in
+ *  1..SK_MAX_SAMPLES, over the window [win_begin, win_begin + n_pos).  rate_sets[0] is the candidate set (in the reference always the
+ *  log-linear ramp), rate_sets[1] the shared set or, with is_sample_specific_rates, rate_sets[1 + s] sample s's.  out[n_keys],
+ *  rates[n_keys * n_samples], totals[2]: candidates, undecided keys.  All struct padding is zero.  Refused with a message: n_samples
+ *  outside 1..SK_MAX_SAMPLES, a rate outside [0, 1], a rate set of no or more than SK_RATE_MAX_SIZES sizes or with a count outside
+ *  1..SK_RATE_MAX_COUNTS, papprox not ascending, observations outside obs_cap, a breakpoint observation whose key the table lacks,
+ *  negative sizes. */
+int sk_indel_candidates(int32_t n_samples, const sk_indel_candidate_sample* samples, int32_t win_begin, int32_t n_pos, const sk_indel_table_key* keys,
+                        const sk_indel_table_sample_data* data, int64_t n_keys, const sk_indel_rate_set* rate_sets, const sk_indel_candidate_options* opt,
+                        sk_indel_candidate* out, sk_indel_error_rates* rates, int64_t* totals);
+/** The same on device memory: samples is a HOST array whose pointers are device memory, opt is read on the host (so n_samples and
+ *  papprox are refused here with a message, as by the host entry); the key count is dev_table_totals[0] as sk_indel_table_dev left it and
+ *  never visits the host; dev_out has room for key_cap records and dev_rates for key_cap * n_samples; only enqueues.  Other input the
+ *  host entry would refuse, or more keys than key_cap, raises the sticky device flag (sk_check_device_errors) and leaves zeroed output:
+ *  every record of dev_out and dev_rates and both totals 0.  Records past the key count are zero. */
+int sk_indel_candidates_dev(int32_t n_samples, const sk_indel_candidate_sample* samples, int32_t win_begin, int32_t n_pos, const sk_indel_table_key* dev_keys,
+                            const sk_indel_table_sample_data* dev_data, const int64_t* dev_table_totals, int64_t key_cap, const sk_indel_rate_set* dev_rate_sets,
+                            const sk_indel_candidate_options* opt, sk_indel_candidate* dev_out, sk_indel_error_rates* dev_rates, int64_t* dev_totals,
+                            void* dev_scratch, size_t scratch_bytes, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * SURVEY.md section 8f rank 4, the output side: the non-variant blocks of the gVCF.
  *
  * gvcf_writer::queue_site_record (L/applications/starling/gvcf_writer.cpp:278-302) asks, site after site and per sample, whether the

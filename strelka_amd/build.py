@@ -32,6 +32,7 @@ HIP_SOURCES = [
     "csrc/region_haplotypes.hip",
     "csrc/region_alleles.hip",
     "csrc/indel_table.hip",
+    "csrc/indel_candidates.hip",
     "csrc/gvcf_block.hip",
     "csrc/libm_probe.hip",
     "csrc/libm_probe_germline.hip",

@@ -239,6 +239,7 @@ EXPORTS = [
     "sk_region_haplotypes_seq_bound", "sk_region_haplotypes_support_bound", "sk_region_haplotypes_scratch_bytes", "sk_region_haplotypes", "sk_region_haplotypes_dev",
     "sk_region_alleles_allele_bound", "sk_region_alleles_insert_bound", "sk_region_alleles_scratch_bytes", "sk_region_alleles", "sk_region_alleles_dev", "sk_debug_region_alleles",
     "sk_indel_table_key_bound", "sk_indel_table_id_bound", "sk_indel_table_insert_bound", "sk_indel_table_scratch_bytes", "sk_indel_table", "sk_indel_table_dev",
+    "sk_indel_candidate_options_default", "sk_read_depth_scratch_bytes", "sk_read_depth", "sk_read_depth_dev", "sk_indel_candidates_scratch_bytes", "sk_indel_candidates", "sk_indel_candidates_dev",
     "sk_align_builder_create", "sk_align_builder_destroy", "sk_align_builder_clear", "sk_align_builder_append", "sk_align_builder_add_read",
     "sk_align_builder_finish", "sk_align_builder_error", "sk_align_builder_set_host_threads",
     "sk_align_scores_default", "sk_global_align",
@@ -412,6 +413,18 @@ def lib():
                                      c_void_p, C.c_int64, c_void_p]
         L.sk_indel_table_dev.argtypes = [C.c_int32, c_void_p, c_void_p, C.c_int32, C.c_int32, c_void_p, c_void_p, C.c_int64, C.c_int32, C.c_int64, c_void_p, C.c_int64,
                                          c_void_p, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, c_void_p, C.c_size_t, c_void_p]
+        L.sk_indel_candidate_options_default.argtypes = [c_void_p]
+        L.sk_indel_candidate_options_default.restype = None
+        L.sk_read_depth_scratch_bytes.restype = C.c_size_t
+        L.sk_read_depth_scratch_bytes.argtypes = [C.c_int32]
+        L.sk_read_depth.argtypes = [C.c_int32, c_void_p, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p, C.c_int32, C.c_int32, c_void_p, c_void_p]
+        L.sk_read_depth_dev.argtypes = [C.c_int32, c_void_p, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p, C.c_int32, C.c_int32, c_void_p, c_void_p, c_void_p, C.c_size_t,
+                                        c_void_p]
+        L.sk_indel_candidates_scratch_bytes.restype = C.c_size_t
+        L.sk_indel_candidates_scratch_bytes.argtypes = []
+        L.sk_indel_candidates.argtypes = [C.c_int32, c_void_p, C.c_int32, C.c_int32, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+        L.sk_indel_candidates_dev.argtypes = [C.c_int32, c_void_p, C.c_int32, C.c_int32, c_void_p, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, C.c_size_t, c_void_p]
         L.sk_align_colmat_words.restype = C.c_int64
         L.sk_align_colmat_words.argtypes = [c_void_p]
         L.sk_align_prepare_cols.argtypes = [c_void_p] * 4
@@ -1994,6 +2007,108 @@ def indel_table(ref_seq, ref_offset, samples, regions, prev_end_in=-1, raw=False
     nk = int(totals[0])
     res = dict(keys=keys[:nk], data=data[:nk * n_samples], id_pool=id_pool[:int(totals[1])], insert_pool=insert_pool[:int(totals[2])], totals=totals)
     return res if raw else (indel_table_records(res["keys"], res["data"], res["id_pool"], res["insert_pool"], n_samples), [int(x) for x in totals])
+
+
+RATE_MAX_SIZES, RATE_MAX_COUNTS, ICAND_PAPPROX, ICAND_MAX_BP_OBS = 4, 40, 18, 257
+ICAND_DECIDED, ICAND_AR_PENDING, ICAND_EXACT_BINOMIAL, ICAND_BP_OBS_ORDER = range(4)
+INDEL_RATE_SET_DTYPE = np.dtype([("n_sizes", "<u4"), ("n_counts", "<u4", (RATE_MAX_SIZES,)), ("pad", "<u4", (3,)), ("insertion", "<f8", (RATE_MAX_SIZES, RATE_MAX_COUNTS)),
+                                 ("deletion", "<f8", (RATE_MAX_SIZES, RATE_MAX_COUNTS))])
+INDEL_CANDIDATE_DTYPE = np.dtype([("is_candidate", "u1"), ("undecided", "u1"), ("pad", "<u2"), ("bp_insert_size", "<u4")])
+INDEL_ERROR_RATES_DTYPE = np.dtype([("ref_to_indel", "<f8"), ("indel_to_ref", "<f8"), ("candidate_ref_to_indel", "<f8"), ("candidate_indel_to_ref", "<f8")])
+assert INDEL_RATE_SET_DTYPE.itemsize == 2592 and INDEL_CANDIDATE_DTYPE.itemsize == 8 and INDEL_ERROR_RATES_DTYPE.itemsize == 32
+
+
+class IndelCandidateOptions(C.Structure):  # sk_indel_candidate_options
+    _fields_ = [("papprox", C.c_double * ICAND_PAPPROX), ("log_indel_ref_error_factor", C.c_double), ("max_candidate_depth", C.c_double),
+                ("min_candidate_indel_open_length", C.c_uint32), ("is_indel_ref_error_factor", C.c_uint8), ("is_haplotyping_enabled", C.c_uint8),
+                ("is_candidate_indel_signal_test", C.c_uint8), ("is_sample_specific_rates", C.c_uint8), ("is_count_towards_depth_filter", C.c_uint8 * MAX_SAMPLES)]
+
+
+class IndelCandidateSample(C.Structure):  # sk_indel_candidate_sample
+    _fields_ = [("n_reads", C.c_int32), ("pad", C.c_int32), ("obs_off", c_void_p), ("obs", c_void_p), ("obs_cap", C.c_int64), ("depth1", c_void_p), ("depth2", c_void_p)]
+
+
+assert C.sizeof(IndelCandidateOptions) == 176 and C.sizeof(IndelCandidateSample) == 48
+
+
+def indel_candidate_options(**fields):
+    """the reference's defaults (sk_indel_candidate_options_default: papprox is left zero, caller data) with `fields` set; a list for papprox and
+    is_count_towards_depth_filter"""
+    o = IndelCandidateOptions()
+    lib().sk_indel_candidate_options_default(C.addressof(o))
+    for k, v in fields.items():
+        if k in ("papprox", "is_count_towards_depth_filter"):
+            for i, x in enumerate(v):
+                getattr(o, k)[i] = x
+        else:
+            setattr(o, k, v)
+    return o
+
+
+def pack_rate_set(sizes):
+    """[[(insertion rate, deletion rate) per repeat count] per pattern size] -> one INDEL_RATE_SET_DTYPE record; sizes past what the record
+    holds are cut (the count stays, for the refusal)"""
+    rs = np.zeros((), INDEL_RATE_SET_DTYPE)
+    rs["n_sizes"] = len(sizes)
+    for i, counts in enumerate(sizes[:RATE_MAX_SIZES]):
+        rs["n_counts"][i] = len(counts)
+        for j, (ins, dele) in enumerate(counts[:RATE_MAX_COUNTS]):
+            rs["insertion"][i][j], rs["deletion"][i][j] = ins, dele
+    return rs
+
+
+def pack_paths(reads):
+    """[dict(pos, path [(type, length)])] -> (path_off, n_seg, PATH_SEG_DTYPE-like uint32 pairs, pos) as sk_read_depth takes them"""
+    n = len(reads)
+    path_off = np.zeros(n + 1, np.int64)
+    n_seg = np.zeros(n + 1, np.int32)
+    pos = np.zeros(n + 1, np.int32)
+    segs = []
+    for r, rd in enumerate(reads):
+        path_off[r], n_seg[r], pos[r] = len(segs), len(rd["path"]), rd["pos"]
+        segs += [(int(t), int(l)) for t, l in rd["path"]]
+    path_off[n] = len(segs)
+    return path_off, n_seg, np.array(segs + [(0, 0)], np.uint32).reshape(-1, 2), pos
+
+
+def read_depth(reads, iat, win_begin, n_pos, packed=None):
+    """one sample's reads [dict(pos, path)] and iat -> (depth1, depth2) over [win_begin, win_begin + n_pos) through sk_read_depth; packed:
+    (path_off, n_seg, path, pos, path_cap) instead of the reads"""
+    L = lib()
+    n = len(iat)
+    path_off, n_seg, path, pos, path_cap = packed or (pack_paths(reads) + (None,))
+    path_cap = len(path) - 1 if path_cap is None else path_cap
+    iat_a = np.ascontiguousarray(list(iat) + [0], np.uint8)
+    d1, d2 = np.zeros(max(n_pos, 1), np.uint32), np.zeros(max(n_pos, 1), np.uint32)
+    _check(L.sk_read_depth(n, _p(path_off), _p(n_seg), _p(path), path_cap, _p(pos), _p(iat_a), int(win_begin), int(n_pos), _p(d1), _p(d2)))
+    return d1[:max(n_pos, 0)], d2[:max(n_pos, 0)]
+
+
+def indel_candidates(samples, win_begin, n_pos, keys, data, rate_sets, opt, n_samples=None, n_keys=None):
+    """samples: [dict(n_reads, obs_off, obs (INTAKE_OBS_DTYPE), depth1, depth2)]; keys / data as sk_indel_table leaves them; rate_sets:
+    INDEL_RATE_SET_DTYPE[], the candidate set first -> dict(out INDEL_CANDIDATE_DTYPE[n_keys], rates INDEL_ERROR_RATES_DTYPE[n_keys * n_samples], totals)
+    through sk_indel_candidates"""
+    L = lib()
+    keep = []
+    for s in samples:
+        obs_off = np.ascontiguousarray(s["obs_off"], np.int64)
+        obs = np.ascontiguousarray(s["obs"], INTAKE_OBS_DTYPE)
+        d1, d2 = np.ascontiguousarray(s["depth1"], np.uint32), np.ascontiguousarray(s["depth2"], np.uint32)
+        keep.append((obs_off, obs, d1, d2))
+    ptr = lambda x: None if len(x) == 0 else x.ctypes.data
+    arr = (IndelCandidateSample * max(len(samples), 1))(*[IndelCandidateSample(int(s["n_reads"]), 0, ptr(k[0]), ptr(k[1]), s.get("obs_cap", len(k[1])), ptr(k[2]), ptr(k[3]))
+                                                          for s, k in zip(samples, keep)])
+    n_samples = len(samples) if n_samples is None else n_samples
+    keys = np.ascontiguousarray(keys, INDEL_TABLE_KEY_DTYPE)
+    data = np.ascontiguousarray(data, INDEL_TABLE_SAMPLE_DATA_DTYPE)
+    nk = len(keys) if n_keys is None else n_keys
+    sets = np.ascontiguousarray(rate_sets, INDEL_RATE_SET_DTYPE)
+    out = np.zeros(max(nk, 1), INDEL_CANDIDATE_DTYPE)
+    rates = np.zeros(max(nk, 1) * max(n_samples, 1), INDEL_ERROR_RATES_DTYPE)
+    totals = np.zeros(2, np.int64)
+    _check(L.sk_indel_candidates(n_samples, C.addressof(arr), int(win_begin), int(n_pos), _p(keys) if len(keys) else None, _p(data) if len(data) else None, nk, _p(sets),
+                                 C.addressof(opt), _p(out), _p(rates), _p(totals)))
+    return dict(out=out[:max(nk, 0)], rates=rates[:max(nk, 0) * n_samples], totals=[int(x) for x in totals])
 
 
 BAI_CHUNK_DTYPE = np.dtype([("begin", "<u8"), ("end", "<u8")])

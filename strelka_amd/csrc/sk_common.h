@@ -118,7 +118,9 @@ enum {
     SK_DEVERR_HAPLOTYPES = 8u, // sk_region_haplotypes_dev met a read or a region its host entry refuses, or ran out of a pool
     SK_DEVERR_ALLELES = 16u, // sk_region_alleles_dev met a haplotype record its host entry refuses, or a capacity below its bound
     SK_DEVERR_SYNC_REGIONS = 32u, // sk_sync_active_regions_dev: createActiveRegion's or closeActiveRegion's assertion failed, or marks its host entry refuses
-    SK_DEVERR_INDEL_TABLE = 64u // sk_indel_table_dev met input its host entry refuses, or a capacity below what the arrays hold
+    SK_DEVERR_INDEL_TABLE = 64u, // sk_indel_table_dev met input its host entry refuses, or a capacity below what the arrays hold
+    SK_DEVERR_READ_DEPTH = 128u, // sk_read_depth_dev met an iat above 2 or a path outside path_cap or with a segment type it does not know
+    SK_DEVERR_INDEL_CANDIDATES = 256u // sk_indel_candidates_dev met a rate set, a key count or observations its host entry refuses
 };
 
 SkContext& sk_ctx();

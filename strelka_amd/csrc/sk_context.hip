@@ -396,6 +396,10 @@ int sk_check_device_errors(void)
         return sk_fail("sk_sync_active_regions_dev: a region's start is not before its end anchor (createActiveRegion's assertion), a synchronised region of no positions (closeActiveRegion's assertion), ploidy marks not ascending or other than 1 or 2, or region_cap too small");
     if (flags & SK_DEVERR_INDEL_TABLE)
         return sk_fail("sk_indel_table_dev: an iat above 2, an observation outside its read, a record or support list outside its pools, or a capacity below what the arrays hold");
+    if (flags & SK_DEVERR_READ_DEPTH)
+        return sk_fail("sk_read_depth_dev: an iat above 2, a path outside path_cap, a negative segment count or a segment type the path format does not have");
+    if (flags & SK_DEVERR_INDEL_CANDIDATES)
+        return sk_fail("sk_indel_candidates_dev: a rate outside [0,1], a rate set of no or more than 4 sizes or with a count outside 1..40, more keys than key_cap, observations outside obs_cap, or a breakpoint observation without its key");
     return sk_fail("strelka_amd: a kernel reported an error");
 }
 
