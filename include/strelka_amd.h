@@ -1868,6 +1868,110 @@ int sk_indel_candidates_dev(int32_t n_samples, const sk_indel_candidate_sample* 
                             void* dev_scratch, size_t scratch_bytes, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * The realignment gate: from the indel table and its candidacy to what a realignment job is made of -- the
+ * sk_indel_info fields per key, and per read the alignment zone, whether the read goes on to the search at all
+ * (check_for_candidate_indel_overlap, L/starling_common/starling_read_align.cpp:217-270) and the observed list (is_usable_indel :289-305).
+ *
+ *   rule G1  the log rates: LogValuePair::updateValue (L/blt_util/LogValuePair.hh:44-48) is std::log of the two doubles initializeAuxInfo
+ *            stores (L/starling_common/IndelData.cpp:153-154): ref_to_indel and indel_to_ref of sk_indel_error_rates.  Bit for bit: the
+ *            restated log of csrc/libm_dbl64.h when the host libm is the one restated; a rate of 0 gives -inf, as the host's log does.
+ *   rule G2  the zone and the two cheap tests: is_realignable is !is_overmax (L/starling_common/alignment.cpp:32-50: an INSERT or DELETE
+ *            segment that is neither the path's first nor its last and is longer than max_indel_size); get_alignment_zone over
+ *            get_alignment_range (L/starling_common/alignment_util.cpp:59-85): begin = pos - unalignedPrefixSize, end = pos + reference
+ *            length + unalignedSuffixSize, zone = [max(0, min(begin, end - read_len)), max(end, begin + read_len)); the read's
+ *            realign_buffer_range must be a superset of the zone (starling_read_align.cpp:2045-2050).  A read with a SKIP segment is
+ *            SK_RGATE_SPLICED: declined, as sk_realign_job_add_reads refuses it.  Order: SPLICED, OVERMAX, OUTSIDE_RANGE, then rule G3.
+ *   rule G3  the gate (:217-270): IndelBuffer::rangeIterator(zone) (L/starling_common/IndelBuffer.cpp:76-92) gives the keys; the first
+ *            that intersects the zone's breakpoints (is_range_intersect_indel_breakpoints, L/starling_common/indel_util.cpp:48-63) and
+ *            is a candidate lets the read pass.  A decided candidate among the intersecting keys: SK_RGATE_PASS; none, but an
+ *            intersecting undecided key (sk_indel_candidate.undecided != 0): SK_RGATE_UNDECIDED; otherwise SK_RGATE_NO_CANDIDATE.
+ *   rule G4  what was asked: the reference computes and caches a key's candidate status at the first question about it
+ *            (L/starling_common/IndelBuffer.hh:153-164).  gate_consulted[k] = 1 when some read's gate reached isCandidateIndel(k): k
+ *            intersects that read's zone and no intersecting DECIDED candidate stands before it in key order.  Undecided keys are asked and
+ *            do not end the loop; a read that asked one has asked_undecided set, and the marks it made after that key are an UPPER BOUND:
+ *            had the key turned out a candidate, the reference's loop would have ended there.
+ *   rule G5  the observed lists (:289-305, the set-membership half): for read r of sample s with align id a, every table index k where a is
+ *            in any of the four id sets of (k, s), ascending, each index once (a read may sit in a noise set and, through rule 3 of the
+ *            table, in a support set of one key).  align_id is strictly ascending or NULL (the read's index), the order in which
+ *            read_id_counter::next() hands ids out (L/starling_common/starling_read_buffer.hh:47-50); an id of the pool that belongs to
+ *            none of its sample's reads is refused.
+ *
+ * BATCH SEMANTICS: every key's candidacy is decided before any read asks (as sk_indel_candidates leaves it); the reference asks lazily, read
+ * by read, and caches.  gate_consulted is the union over the call's reads, whatever their order.  On one stream sk_indel_table_dev ->
+ * sk_read_depth_dev -> sk_indel_candidates_dev -> sk_realign_gate_dev run with no host copy; the key count stays on the device.
+ * Out of scope: routing and anything in adapter/; sk_realign_job_* (the job keeps running its own gate); forced and external indels and
+ * notDiscoveredFromReads (both 0 in the sk_indel_info a caller builds from these records); RNA pins; the exact binomial, which stays
+ * declined upstream and surfaces here as SK_RGATE_UNDECIDED; the breakpoint consensus sequence (a breakpoint key's ins_len is 0).
+ * ---------------------------------------------------------------------------------------------------------------- */
+enum { SK_RGATE_NONE = 0, /* not judged: what a refused call leaves */
+       SK_RGATE_PASS, SK_RGATE_OVERMAX, SK_RGATE_OUTSIDE_RANGE, SK_RGATE_NO_CANDIDATE, SK_RGATE_UNDECIDED, SK_RGATE_SPLICED }; /* sk_realign_gate_read.status */
+enum { SK_RGATE_SORT_CAP = 64 }; /* an observed list up to this long is sorted in one wave's registers; a longer one in several passes */
+typedef struct sk_realign_gate_sample { /* one sample's reads (host or device memory) */
+    int32_t n_reads, pad;
+    const int32_t* pos;          /* [n_reads]; pos, path_off, n_seg, path, path_cap as sk_read_depth takes them */
+    const int64_t* path_off;
+    const int32_t* n_seg;
+    const sk_path_seg* path;
+    int64_t path_cap;            /* the room of path */
+    const int32_t* read_len;     /* [n_reads] */
+    const uint32_t* align_id;    /* [n_reads] strictly ascending; NULL: the read's index */
+    const int32_t* realign_begin;/* [n_reads] the caller's realign_buffer_range */
+    const int32_t* realign_end;
+} sk_realign_gate_sample;
+typedef struct sk_realign_gate_key { /* per key: the fields of sk_indel_info the samples share */
+    int32_t pos, type;
+    uint32_t del_len, ins_len;   /* key.insertSequence is insert_pool[ins_off .. ins_off + ins_len) of the TABLE's pool */
+    int64_t ins_off;
+    int32_t active_region_id;
+    uint8_t is_candidate;        /* sk_indel_candidate.is_candidate */
+    uint8_t undecided;           /* SK_ICAND_*, passed through */
+    uint8_t gate_consulted;      /* rule G4 */
+    uint8_t pad;
+    int8_t haplotype_id[SK_MAX_SAMPLES];
+    uint8_t is_haplotyping_bypassed[SK_MAX_SAMPLES];
+} sk_realign_gate_key;
+typedef struct sk_realign_gate_log_rates { /* per (key, sample): logs[key * n_samples + sample] */
+    double ref_to_indel_log_prob, indel_to_ref_log_prob;
+} sk_realign_gate_log_rates;
+typedef struct sk_realign_gate_read { /* per (sample, read) */
+    int32_t zone_begin, zone_end;
+    uint8_t status;              /* SK_RGATE_* */
+    uint8_t asked_undecided;     /* rule G4 */
+    uint16_t pad;
+} sk_realign_gate_read;
+typedef struct sk_realign_gate_sample_out { /* one sample's outputs (host or device memory) */
+    sk_realign_gate_read* reads; /* [n_reads] */
+    int64_t* observed_off;       /* [n_reads + 1] */
+    int32_t* observed;           /* table indices, ascending and unique per read */
+    int64_t observed_cap;        /* the room of observed: at least sk_realign_gate_observed_bound of the table's ids */
+} sk_realign_gate_sample_out;
+/** Room for one sample's observed entries: every id of the pool could be one.  Host arithmetic only; -1 for a negative count. */
+int64_t sk_realign_gate_observed_bound(int64_t n_ids);
+/** Bytes of device scratch sk_realign_gate_dev needs.  Host arithmetic only; 0 for arguments out of range. */
+size_t sk_realign_gate_scratch_bytes(int32_t n_samples, int64_t key_cap, int64_t id_cap);
+/** Rules G1-G5.  samples[n_samples] / outs[n_samples], n_samples in 1..SK_MAX_SAMPLES; keys[n_keys], data[n_keys * n_samples] and
+ *  id_pool[n_ids] as sk_indel_table leaves them (n_keys = its totals[0], n_ids = its totals[1]); cand[n_keys] and rates[n_keys * n_samples]
+ *  as sk_indel_candidates leaves them.  keys_out[n_keys], logs[n_keys * n_samples], totals[2 + SK_MAX_SAMPLES]: reads that pass, reads
+ *  undecided, observed entries per sample.  All struct padding is zero.  Refused with a message: n_samples outside 1..SK_MAX_SAMPLES,
+ *  negative sizes, a negative n_seg or read_len, a path outside path_cap, a segment type above SK_SEG_SEQ_MISMATCH, align_id not strictly
+ *  ascending, id sets that do not tile id_pool in (key, sample, set) order, an id that belongs to none of its sample's reads,
+ *  observed_cap below sk_realign_gate_observed_bound(n_ids). */
+int sk_realign_gate(int32_t n_samples, const sk_realign_gate_sample* samples, const sk_indel_table_key* keys, const sk_indel_table_sample_data* data,
+                    const uint32_t* id_pool, int64_t n_keys, int64_t n_ids, const sk_indel_candidate* cand, const sk_indel_error_rates* rates,
+                    uint32_t max_indel_size, sk_realign_gate_key* keys_out, sk_realign_gate_log_rates* logs, const sk_realign_gate_sample_out* outs,
+                    int64_t* totals);
+/** The same on device memory: samples and outs are HOST arrays whose pointers are device memory; the key and id counts are
+ *  dev_table_totals[0] and [1] as sk_indel_table_dev left them and never visit the host; dev_keys_out has room for key_cap records,
+ *  dev_logs for key_cap * n_samples; only enqueues.  What the host can read (n_samples, sizes, null pointers, the scratch) is refused here
+ *  with a message.  Other input the host entry would refuse, more keys than key_cap, more ids than id_cap or an observed_cap below the ids'
+ *  count raises the sticky device flag (sk_check_device_errors) and leaves zeroed output: every record, offset and total 0 (status
+ *  SK_RGATE_NONE).  Records past the key count are zero. */
+int sk_realign_gate_dev(int32_t n_samples, const sk_realign_gate_sample* samples, const sk_indel_table_key* dev_keys, const sk_indel_table_sample_data* dev_data,
+                        const uint32_t* dev_id_pool, const int64_t* dev_table_totals, int64_t key_cap, int64_t id_cap, const sk_indel_candidate* dev_cand,
+                        const sk_indel_error_rates* dev_rates, uint32_t max_indel_size, sk_realign_gate_key* dev_keys_out, sk_realign_gate_log_rates* dev_logs,
+                        const sk_realign_gate_sample_out* outs, int64_t* dev_totals, void* dev_scratch, size_t scratch_bytes, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * SURVEY.md section 8f rank 4, the output side: the non-variant blocks of the gVCF.
  *
  * gvcf_writer::queue_site_record (L/applications/starling/gvcf_writer.cpp:278-302) asks, site after site and per sample, whether the

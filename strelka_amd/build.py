@@ -33,6 +33,7 @@ HIP_SOURCES = [
     "csrc/region_alleles.hip",
     "csrc/indel_table.hip",
     "csrc/indel_candidates.hip",
+    "csrc/realign_gate.hip",
     "csrc/gvcf_block.hip",
     "csrc/libm_probe.hip",
     "csrc/libm_probe_germline.hip",

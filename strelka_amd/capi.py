@@ -240,6 +240,7 @@ EXPORTS = [
     "sk_region_alleles_allele_bound", "sk_region_alleles_insert_bound", "sk_region_alleles_scratch_bytes", "sk_region_alleles", "sk_region_alleles_dev", "sk_debug_region_alleles",
     "sk_indel_table_key_bound", "sk_indel_table_id_bound", "sk_indel_table_insert_bound", "sk_indel_table_scratch_bytes", "sk_indel_table", "sk_indel_table_dev",
     "sk_indel_candidate_options_default", "sk_read_depth_scratch_bytes", "sk_read_depth", "sk_read_depth_dev", "sk_indel_candidates_scratch_bytes", "sk_indel_candidates", "sk_indel_candidates_dev",
+    "sk_realign_gate_observed_bound", "sk_realign_gate_scratch_bytes", "sk_realign_gate", "sk_realign_gate_dev",
     "sk_align_builder_create", "sk_align_builder_destroy", "sk_align_builder_clear", "sk_align_builder_append", "sk_align_builder_add_read",
     "sk_align_builder_finish", "sk_align_builder_error", "sk_align_builder_set_host_threads",
     "sk_align_scores_default", "sk_global_align",
@@ -425,6 +426,14 @@ def lib():
         L.sk_indel_candidates.argtypes = [C.c_int32, c_void_p, C.c_int32, C.c_int32, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
         L.sk_indel_candidates_dev.argtypes = [C.c_int32, c_void_p, C.c_int32, C.c_int32, c_void_p, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                               c_void_p, C.c_size_t, c_void_p]
+        L.sk_realign_gate_observed_bound.restype = C.c_int64
+        L.sk_realign_gate_observed_bound.argtypes = [C.c_int64]
+        L.sk_realign_gate_scratch_bytes.restype = C.c_size_t
+        L.sk_realign_gate_scratch_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int64]
+        L.sk_realign_gate.argtypes = [C.c_int32, c_void_p, c_void_p, c_void_p, c_void_p, C.c_int64, C.c_int64, c_void_p, c_void_p, C.c_uint32, c_void_p, c_void_p, c_void_p,
+                                      c_void_p]
+        L.sk_realign_gate_dev.argtypes = [C.c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, C.c_int64, C.c_int64, c_void_p, c_void_p, C.c_uint32, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, C.c_size_t, c_void_p]
         L.sk_align_colmat_words.restype = C.c_int64
         L.sk_align_colmat_words.argtypes = [c_void_p]
         L.sk_align_prepare_cols.argtypes = [c_void_p] * 4
@@ -2109,6 +2118,110 @@ def indel_candidates(samples, win_begin, n_pos, keys, data, rate_sets, opt, n_sa
     _check(L.sk_indel_candidates(n_samples, C.addressof(arr), int(win_begin), int(n_pos), _p(keys) if len(keys) else None, _p(data) if len(data) else None, nk, _p(sets),
                                  C.addressof(opt), _p(out), _p(rates), _p(totals)))
     return dict(out=out[:max(nk, 0)], rates=rates[:max(nk, 0) * n_samples], totals=[int(x) for x in totals])
+
+
+RGATE_NONE, RGATE_PASS, RGATE_OVERMAX, RGATE_OUTSIDE_RANGE, RGATE_NO_CANDIDATE, RGATE_UNDECIDED, RGATE_SPLICED = range(7)
+RGATE_SORT_CAP = 64
+REALIGN_GATE_KEY_DTYPE = np.dtype([("pos", "<i4"), ("type", "<i4"), ("del_len", "<u4"), ("ins_len", "<u4"), ("ins_off", "<i8"), ("active_region_id", "<i4"), ("is_candidate", "u1"),
+                                   ("undecided", "u1"), ("gate_consulted", "u1"), ("pad", "u1"), ("haplotype_id", "i1", (MAX_SAMPLES,)),
+                                   ("is_haplotyping_bypassed", "u1", (MAX_SAMPLES,))])
+REALIGN_GATE_LOG_RATES_DTYPE = np.dtype([("ref_to_indel_log_prob", "<f8"), ("indel_to_ref_log_prob", "<f8")])
+REALIGN_GATE_READ_DTYPE = np.dtype([("zone_begin", "<i4"), ("zone_end", "<i4"), ("status", "u1"), ("asked_undecided", "u1"), ("pad", "<u2")])
+assert REALIGN_GATE_KEY_DTYPE.itemsize == 48 and REALIGN_GATE_LOG_RATES_DTYPE.itemsize == 16 and REALIGN_GATE_READ_DTYPE.itemsize == 12
+
+
+class RealignGateSample(C.Structure):  # sk_realign_gate_sample
+    _fields_ = [("n_reads", C.c_int32), ("pad", C.c_int32), ("pos", c_void_p), ("path_off", c_void_p), ("n_seg", c_void_p), ("path", c_void_p), ("path_cap", C.c_int64),
+                ("read_len", c_void_p), ("align_id", c_void_p), ("realign_begin", c_void_p), ("realign_end", c_void_p)]
+
+
+class RealignGateSampleOut(C.Structure):  # sk_realign_gate_sample_out
+    _fields_ = [("reads", c_void_p), ("observed_off", c_void_p), ("observed", c_void_p), ("observed_cap", C.c_int64)]
+
+
+assert C.sizeof(RealignGateSample) == 80 and C.sizeof(RealignGateSampleOut) == 32
+
+
+def realign_gate_observed_bound(n_ids):
+    """room for one sample's observed entries; host arithmetic, works without a device"""
+    return int(lib().sk_realign_gate_observed_bound(int(n_ids)))
+
+
+def pack_gate_sample(reads, align_id=None):
+    """[dict(pos, path [(type, length)], read_len, realign (begin, end))] and the reads' align ids (None: their indices) -> the arrays of one
+    sk_realign_gate_sample, each with one element of slack: dict(n_reads, pos, path_off, n_seg, path, path_cap, read_len, align_id,
+    realign_begin, realign_end)"""
+    path_off, n_seg, path, pos = pack_paths(reads)
+    n = len(reads)
+    return dict(n_reads=n, pos=pos, path_off=path_off, n_seg=n_seg, path=path, path_cap=len(path) - 1,
+                read_len=np.array([int(r["read_len"]) for r in reads] + [0], np.int32),
+                align_id=None if align_id is None else np.array(list(align_id) + [0], np.uint32),
+                realign_begin=np.array([int(r["realign"][0]) for r in reads] + [0], np.int32), realign_end=np.array([int(r["realign"][1]) for r in reads] + [0], np.int32))
+
+
+def realign_gate_sample_struct(p, ptr=None):
+    """pack_gate_sample's dict -> RealignGateSample over its arrays (ptr: array -> address; the default takes host arrays)"""
+    ptr = ptr or (lambda x: x.ctypes.data)
+    return RealignGateSample(int(p["n_reads"]), 0, ptr(p["pos"]), ptr(p["path_off"]), ptr(p["n_seg"]), ptr(p["path"]), int(p["path_cap"]), ptr(p["read_len"]),
+                             None if p["align_id"] is None else ptr(p["align_id"]), ptr(p["realign_begin"]), ptr(p["realign_end"]))
+
+
+def realign_gate(samples, keys, data, id_pool, cand, rates, max_indel_size, n_samples=None, n_keys=None, n_ids=None, observed_cap=None, slack=0):
+    """samples: [pack_gate_sample's dicts]; keys / data / id_pool as sk_indel_table leaves them, cand / rates as sk_indel_candidates leaves them ->
+    dict(keys REALIGN_GATE_KEY_DTYPE[n_keys], logs REALIGN_GATE_LOG_RATES_DTYPE[n_keys * n_samples], samples [dict(reads REALIGN_GATE_READ_DTYPE[],
+    observed_off, observed)], totals [reads that pass, reads undecided, observed entries per sample]) through sk_realign_gate.  slack: so
+    many extra elements of 0x5a bytes behind every output array, returned with it (the tests' canaries)"""
+    L = lib()
+    n_samples = len(samples) if n_samples is None else n_samples
+    keys = np.ascontiguousarray(keys, INDEL_TABLE_KEY_DTYPE)
+    data = np.ascontiguousarray(data, INDEL_TABLE_SAMPLE_DATA_DTYPE)
+    id_pool = np.ascontiguousarray(id_pool, np.uint32)
+    cand = np.ascontiguousarray(cand, INDEL_CANDIDATE_DTYPE)
+    rates = np.ascontiguousarray(rates, INDEL_ERROR_RATES_DTYPE)
+    nk = len(keys) if n_keys is None else n_keys
+    ni = len(id_pool) if n_ids is None else n_ids
+    ns = max(n_samples, 1)
+
+    def room(n, dtype):
+        a = np.zeros(max(n, 0) + max(slack, 1), dtype)
+        a.view(np.uint8)[max(n, 0) * a.dtype.itemsize:] = 0x5a
+        return a
+    keys_out, logs = room(nk, REALIGN_GATE_KEY_DTYPE), room(nk * ns, REALIGN_GATE_LOG_RATES_DTYPE)
+    totals = np.zeros(2 + MAX_SAMPLES, np.int64)
+    cap = max(ni, 0) if observed_cap is None else observed_cap
+    outs = [dict(reads=room(int(p["n_reads"]), REALIGN_GATE_READ_DTYPE), observed_off=room(int(p["n_reads"]) + 1, np.int64), observed=room(cap, np.int32)) for p in samples]
+    arr_in = (RealignGateSample * max(len(samples), 1))(*[realign_gate_sample_struct(p) for p in samples])
+    arr_out = (RealignGateSampleOut * max(len(samples), 1))(*[RealignGateSampleOut(o["reads"].ctypes.data, o["observed_off"].ctypes.data, o["observed"].ctypes.data, cap) for o in outs])
+    ptr = lambda x: _p(x) if len(x) else None
+    _check(L.sk_realign_gate(n_samples, C.addressof(arr_in), ptr(keys), ptr(data), ptr(id_pool), nk, ni, ptr(cand), ptr(rates), int(max_indel_size), _p(keys_out), _p(logs),
+                             C.addressof(arr_out), _p(totals)))
+    cut = (lambda a, n: a[:max(n, 0) + slack])
+    res = dict(keys=cut(keys_out, nk), logs=cut(logs, nk * ns), totals=[int(x) for x in totals], samples=[])
+    for s, (p, o) in enumerate(zip(samples, outs)):
+        n = int(p["n_reads"])
+        res["samples"].append(dict(reads=cut(o["reads"], n), observed_off=cut(o["observed_off"], n + 1), observed=cut(o["observed"], cap), n_observed=int(totals[2 + s])))
+    return res
+
+
+def realign_job_inputs(gate, sample, reads, insert_pool):
+    """what a realignment job of one sample is made of, from sk_realign_gate's outputs: gate: realign_gate's result (or the same arrays read back from
+    the device); reads: the sample's [dict(code, qual, pos, path, fwd, map_level, realign)] -> (indels as RealignJob.set_indels takes them, reads as
+    RealignJob.add_reads takes them).  Every read is handed on, whatever its status: the job runs its own gate."""
+    n_samples = len(gate["logs"]) // max(len(gate["keys"]), 1) if len(gate["keys"]) else 1
+    indels = []
+    for k, key in enumerate(gate["keys"]):
+        io, il = int(key["ins_off"]), int(key["ins_len"])
+        lg = gate["logs"][k * n_samples + sample]
+        indels.append(dict(pos=int(key["pos"]), type=int(key["type"]), del_len=int(key["del_len"]), ins_seq=bytes(insert_pool[io:io + il]).decode("latin-1"),
+                           is_candidate=int(key["is_candidate"]), r2i=float(lg["ref_to_indel_log_prob"]), i2r=float(lg["indel_to_ref_log_prob"]),
+                           arid=int(key["active_region_id"]), hap=[int(x) for x in key["haplotype_id"]], bypass=[int(x) for x in key["is_haplotyping_bypassed"]]))
+    so = gate["samples"][sample]
+    out = []
+    for r, rd in enumerate(reads):
+        b, e = int(so["observed_off"][r]), int(so["observed_off"][r + 1])
+        out.append((rd["code"], rd["qual"], rd["pos"], rd["path"], rd.get("fwd", True), rd.get("map_level", MAPLEVEL["TIER1"]), sample, tuple(rd["realign"]),
+                    [int(x) for x in so["observed"][b:e]]))
+    return indels, out
 
 
 BAI_CHUNK_DTYPE = np.dtype([("begin", "<u8"), ("end", "<u8")])

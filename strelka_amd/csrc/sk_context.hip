@@ -400,6 +400,8 @@ int sk_check_device_errors(void)
         return sk_fail("sk_read_depth_dev: an iat above 2, a path outside path_cap, a negative segment count or a segment type the path format does not have");
     if (flags & SK_DEVERR_INDEL_CANDIDATES)
         return sk_fail("sk_indel_candidates_dev: a rate outside [0,1], a rate set of no or more than 4 sizes or with a count outside 1..40, more keys than key_cap, observations outside obs_cap, or a breakpoint observation without its key");
+    if (flags & SK_DEVERR_REALIGN_GATE)
+        return sk_fail("sk_realign_gate_dev: a path outside path_cap, a negative segment count or read length, a segment type the path format does not have, align ids not strictly ascending, id sets that do not tile the id pool, an id that belongs to none of its sample's reads, more keys than key_cap, more ids than id_cap, or observed_cap below the ids' count");
     return sk_fail("strelka_amd: a kernel reported an error");
 }
 
