@@ -1972,6 +1972,117 @@ int sk_realign_gate_dev(int32_t n_samples, const sk_realign_gate_sample* samples
                         const sk_realign_gate_sample_out* outs, int64_t* dev_totals, void* dev_scratch, size_t scratch_bytes, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * The realignment preamble: from the gate's outputs to what the device realignment job starts from -- one
+ * record per passing read, holding what getCandidateAlignments (L/starling_common/starling_read_align.cpp:1816-1957) hands to
+ * candidate_alignment_search.  The rules, restated container-free in csrc/preamble_core.h:
+ *
+ *   rule P1  input normalisation (enumerate_read, :2001-2057, DNA reads): is_edge_readref_len_segment (L/blt_util/align_path.cpp:824-846)
+ *            -> matchify_edge_indels(lead, trail) (L/starling_common/alignment_util.cpp:92-198); a path that is still soft clipped ->
+ *            matchify_edge_segment_type(SOFT_CLIP) (:130-174).  A normalised pos < 0 ends the read: SK_RPRE_NEGATIVE_POS, no record, and a
+ *            job reports no candidate alignment for it.
+ *   rule P2  edge keys (:1479-1522): the leading and the trailing INSERT or DELETE outside the match segments, looked up in the table by
+ *            (pos, type, del_len, insert bytes); the insert bytes are the read's codes through bam_seq::get_char
+ *            (L/htsapi/bam_seq.hh:30-46), positions past the codes read 'N'.  An absent edge key is what sk_realign_job_add_reads refuses
+ *            ("... edge indel of the input alignment is not in the indel table"): SK_RPRE_EDGE_KEY_MISSING, no record.
+ *   rule P3  the initial status map: add_indels_in_range (:311-366) over soft_clip_range of the normalised alignment
+ *            (L/starling_common/alignment_util.cpp:45-56); is_usable_indel (:289-305) is is_candidate || observed, candidacy asked first;
+ *            every key asked sets preamble_consulted[k] = 1.  More than SK_RPRE_K entries: SK_RPRE_CAP_K.
+ *   rule P4  the exemplar's own keys (getAlignmentIndels, L/starling_common/CandidateAlignment.cpp:59-177, include_mismatches): edge
+ *            segments, swap segments (is_segment_swap_start, align_path.cpp:868-895), plain indels, the breakpoint pair above
+ *            max_indel_size; mismatch keys only when the table holds any.  A non-mismatch key absent from the table or the map is the
+ *            job's "Exemplar alignment contains indel not found in the overlap indel set": SK_RPRE_EXEMPLAR_KEY_MISSING; an absent
+ *            mismatch key is skipped.  Found keys are present and in_original; a found mismatch key has the alignment recomputed by
+ *            make_start_pos_alignment (:394-584) over the found set, and a failure there is SK_RPRE_CAP_P.
+ *   rule P5  the toggle order: present entries ascending, then absent ones, then sort_remove_only_indels_last (:724-751); a clipped path
+ *            (is_clipped, align_path.cpp:770-781) goes through clip_clipper (:460-504): hc_lead, hc_trail, sc_lead, sc_trail, clipped.
+ *            read_length is the clipped read's; exemplar_range is from before the clip.
+ *
+ * Capacities decline a read, nothing is truncated: a table above 32 000 keys (SK_RPRE_CAP_K: the record's indices are int16), a status map
+ * above SK_RPRE_K, an observed list above SK_RPRE_OBS (SK_RPRE_CAP_OBS), a path above SK_RPRE_P segments or a segment or read length above
+ * 0xffff (SK_RPRE_CAP_P).  A declined read takes the host path through plain sk_realign_job_add_reads.  A read over a path capacity is
+ * declined before P2 looks for its keys; the job, which checks its capacities last, is what then names a missing key.
+ * Out of scope: routing and adapter/; RNA pins; forced and external indels.
+ * ---------------------------------------------------------------------------------------------------------------- */
+enum { SK_RPRE_NONE = 0, /* not judged: what a refused call leaves */
+       SK_RPRE_OK, SK_RPRE_NOT_PASSED /* the gate's status is not SK_RGATE_PASS */, SK_RPRE_NEGATIVE_POS, SK_RPRE_EDGE_KEY_MISSING, SK_RPRE_EXEMPLAR_KEY_MISSING,
+       SK_RPRE_CAP_K, SK_RPRE_CAP_OBS, SK_RPRE_CAP_P, SK_RPRE_N_STATUS };
+enum { SK_RPRE_K = 40, SK_RPRE_P = 48, SK_RPRE_OBS = 64, SK_RPRE_N_TOTALS = 1 + SK_RPRE_N_STATUS };
+typedef struct sk_realign_prepared_range { int32_t b, e; uint8_t has_b, has_e, pad[2]; } sk_realign_prepared_range;
+typedef struct sk_realign_prepared_seg { uint16_t type, length; } sk_realign_prepared_seg;
+typedef struct sk_realign_prepared_status { int16_t idx; uint8_t is_present, is_remove_only, in_original, pad; } sk_realign_prepared_status;
+typedef struct sk_realign_prepared_alignment { /* the normalised and clipped input alignment with its edge-indel indices */
+    int32_t pos;
+    int16_t lead, trail;         /* table index of the leading / trailing edge indel, -1: none */
+    uint8_t is_fwd_strand, n_seg, n_indels /* 0 */, pad;
+    sk_realign_prepared_seg path[SK_RPRE_P];
+    int16_t indels[SK_RPRE_K + 2]; /* zero: the search fills it in its leaves */
+} sk_realign_prepared_alignment;
+typedef struct sk_realign_prepared_read { /* layout-identical to skcore::PRead (csrc/realign_core.h); indices are into the table in key order; unused entries and padding are zero */
+    int32_t realign_begin, realign_end;
+    int32_t read_length;         /* of the clipped read */
+    int32_t sample;
+    sk_realign_prepared_range exemplar_range;
+    sk_realign_prepared_alignment alignment;
+    sk_realign_prepared_status status_map[SK_RPRE_K]; /* ascending idx */
+    int16_t order[SK_RPRE_K];
+    int16_t observed[SK_RPRE_OBS]; /* ascending */
+    uint8_t n_status, n_order, n_observed, clipped;
+    uint32_t hc_lead, hc_trail, sc_lead, sc_trail;
+} sk_realign_prepared_read;
+typedef struct sk_realign_prepared_source { int32_t sample, read; } sk_realign_prepared_source;
+typedef struct sk_realign_preamble_sample { /* per sample, beside its sk_realign_gate_sample and sk_realign_gate_sample_out (host or device memory) */
+    const uint8_t* read_code;    /* BAM 4-bit codes, one per byte; read r's are [read_off[r], read_off[r + 1]) */
+    const int64_t* read_off;     /* [n_reads + 1] ascending; a read longer than its codes reads 'N' past them */
+    int64_t code_cap;            /* the room of read_code */
+    const uint8_t* is_fwd_strand;/* [n_reads]; NULL: every read is on the forward strand */
+    uint8_t* status;             /* OUT [n_reads] SK_RPRE_* */
+} sk_realign_preamble_sample;
+/** Bytes of device scratch sk_realign_preamble_dev needs.  Host arithmetic only; 0 for arguments out of range. */
+size_t sk_realign_preamble_scratch_bytes(int32_t n_samples, int64_t key_cap, int64_t record_cap);
+/** Rules P1-P5.  samples[n_samples] as sk_realign_gate took them; gate[n_samples]: reads, observed_off and observed as it left them (inputs
+ *  here); pre[n_samples]; keys[n_keys] as sk_realign_gate left them, in table order; insert_pool[insert_len]: the table's; ref: the job's
+ *  reference segment (read by P4's mismatch branch only; positions outside it read 'N').  records[record_cap] and source[record_cap]:
+ *  the records of the reads whose gate status is SK_RGATE_PASS and whose preamble status is SK_RPRE_OK, in (sample, read) order, and
+ *  where each comes from; preamble_consulted[n_keys]; totals[SK_RPRE_N_TOTALS]: the record count, then the reads per status
+ *  (totals[1 + SK_RPRE_x]).  Refused with a message: what sk_realign_gate refuses of the reads, a gate status above SK_RGATE_SPLICED, a
+ *  read_off that descends or leaves code_cap, an observed list outside observed_cap, not strictly ascending or with an index outside the
+ *  table, keys whose positions descend or whose insert lies outside the pool, a key type outside SK_INDEL_INDEL..SK_INDEL_BP_RIGHT, record_cap below the
+ *  number of reads that pass the gate. */
+int sk_realign_preamble(int32_t n_samples, const sk_realign_gate_sample* samples, const sk_realign_gate_sample_out* gate, const sk_realign_preamble_sample* pre,
+                        const sk_realign_gate_key* keys, int64_t n_keys, const uint8_t* insert_pool, int64_t insert_len, const char* ref, int32_t ref_offset,
+                        int32_t ref_len, uint32_t max_indel_size, sk_realign_prepared_read* records, sk_realign_prepared_source* source, int64_t record_cap,
+                        uint8_t* preamble_consulted, int64_t* totals);
+/** The same on device memory: samples, gate and pre are HOST arrays whose pointers are device memory; the key count is dev_table_totals[0]
+ *  as sk_indel_table_dev left it and never visits the host; only enqueues, so on one stream ... -> sk_realign_gate_dev ->
+ *  sk_realign_preamble_dev run with no host copy.  What the host can read is refused here with a message.  Other input the host entry
+ *  would refuse, or more keys than key_cap, raises the sticky device flag (sk_check_device_errors) and leaves zeroed output: every
+ *  record, source, status byte, mark and total 0.  Records past the record count are zero. */
+int sk_realign_preamble_dev(int32_t n_samples, const sk_realign_gate_sample* samples, const sk_realign_gate_sample_out* gate, const sk_realign_preamble_sample* pre,
+                            const sk_realign_gate_key* dev_keys, const int64_t* dev_table_totals, int64_t key_cap, const uint8_t* dev_insert_pool, int64_t insert_cap,
+                            const char* dev_ref, int32_t ref_offset, int32_t ref_len, uint32_t max_indel_size, sk_realign_prepared_read* dev_records,
+                            sk_realign_prepared_source* dev_source, int64_t record_cap, uint8_t* dev_preamble_consulted, int64_t* dev_totals, void* dev_scratch,
+                            size_t scratch_bytes, void* hip_stream);
+/** TEST HOOK: sk_realign_preamble's arguments and results, computed on the host by the same csrc/preamble_core.h the kernels run, through
+ *  the same argument record; needs no device. */
+int sk_debug_realign_preamble_host(int32_t n_samples, const sk_realign_gate_sample* samples, const sk_realign_gate_sample_out* gate, const sk_realign_preamble_sample* pre,
+                                   const sk_realign_gate_key* keys, int64_t n_keys, const uint8_t* insert_pool, int64_t insert_len, const char* ref, int32_t ref_offset,
+                                   int32_t ref_len, uint32_t max_indel_size, sk_realign_prepared_read* records, sk_realign_prepared_source* source, int64_t record_cap,
+                                   uint8_t* preamble_consulted, int64_t* totals);
+/** Reads whose gate and preamble ran elsewhere (sk_realign_gate, sk_realign_preamble): prepared[i] is read i's record and becomes what the
+ *  device search starts from; neither the host gate nor the host preamble runs, and the record's observed list is taken as given.
+ *  Requires sk_realign_options.enumeration == 2, and a table whose order is the order of the keys the records index: set_indels given
+ *  the gate's keys in table order.  Each read is validated as sk_realign_job_add_reads validates it (lengths, pointers, sample index, SKIP
+ *  segments, the path's read length, a quality above 70); a record with an index outside the table or a count above SK_RPRE_K /
+ *  SK_RPRE_P / SK_RPRE_OBS is refused.  Returns the first read's index, or -1 and adds nothing.  CONSULTED MARKS: the job reports only
+ *  the marks of what it ran itself (the search); the caller owns the marks of the stages that were skipped, gate_consulted |
+ *  preamble_consulted, and ORs them to sk_realign_job_indels_consulted. */
+int sk_realign_job_add_reads_prepared(sk_realign_job* job, const sk_read_input* reads, const sk_realign_prepared_read* prepared, int32_t n);
+/** TEST HOOK: the record the job's own preamble (to_core_read) makes for read read_index, which was added by sk_realign_job_add_read[s] in any
+ *  enumeration mode; padding zero.  Returns 0 and the record, 1 when the read has none (it left at the gate, at a capacity or at a
+ *  negative position), -1 for a bad argument.  Asks only what adding the read asked: the job's consulted marks do not change. */
+int sk_debug_realign_job_prepared(const sk_realign_job* job, int32_t read_index, sk_realign_prepared_read* out);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * SURVEY.md section 8f rank 4, the output side: the non-variant blocks of the gVCF.
  *
  * gvcf_writer::queue_site_record (L/applications/starling/gvcf_writer.cpp:278-302) asks, site after site and per sample, whether the

@@ -34,6 +34,7 @@ HIP_SOURCES = [
     "csrc/indel_table.hip",
     "csrc/indel_candidates.hip",
     "csrc/realign_gate.hip",
+    "csrc/realign_preamble.hip",
     "csrc/gvcf_block.hip",
     "csrc/libm_probe.hip",
     "csrc/libm_probe_germline.hip",

@@ -241,6 +241,8 @@ EXPORTS = [
     "sk_indel_table_key_bound", "sk_indel_table_id_bound", "sk_indel_table_insert_bound", "sk_indel_table_scratch_bytes", "sk_indel_table", "sk_indel_table_dev",
     "sk_indel_candidate_options_default", "sk_read_depth_scratch_bytes", "sk_read_depth", "sk_read_depth_dev", "sk_indel_candidates_scratch_bytes", "sk_indel_candidates", "sk_indel_candidates_dev",
     "sk_realign_gate_observed_bound", "sk_realign_gate_scratch_bytes", "sk_realign_gate", "sk_realign_gate_dev",
+    "sk_realign_preamble_scratch_bytes", "sk_realign_preamble", "sk_realign_preamble_dev", "sk_debug_realign_preamble_host", "sk_realign_job_add_reads_prepared",
+    "sk_debug_realign_job_prepared",
     "sk_align_builder_create", "sk_align_builder_destroy", "sk_align_builder_clear", "sk_align_builder_append", "sk_align_builder_add_read",
     "sk_align_builder_finish", "sk_align_builder_error", "sk_align_builder_set_host_threads",
     "sk_align_scores_default", "sk_global_align",
@@ -434,6 +436,15 @@ def lib():
                                       c_void_p]
         L.sk_realign_gate_dev.argtypes = [C.c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, C.c_int64, C.c_int64, c_void_p, c_void_p, C.c_uint32, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, C.c_size_t, c_void_p]
+        L.sk_realign_preamble_scratch_bytes.restype = C.c_size_t
+        L.sk_realign_preamble_scratch_bytes.argtypes = [C.c_int32, C.c_int64, C.c_int64]
+        for f in (L.sk_realign_preamble, L.sk_debug_realign_preamble_host):
+            f.argtypes = [C.c_int32, c_void_p, c_void_p, c_void_p, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_int32, C.c_int32, C.c_uint32, c_void_p, c_void_p,
+                          C.c_int64, c_void_p, c_void_p]
+        L.sk_realign_preamble_dev.argtypes = [C.c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, C.c_int64, c_void_p, C.c_int64, c_void_p, C.c_int32, C.c_int32,
+                                              C.c_uint32, c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p, c_void_p, C.c_size_t, c_void_p]
+        L.sk_realign_job_add_reads_prepared.argtypes = [c_void_p, c_void_p, c_void_p, C.c_int32]
+        L.sk_debug_realign_job_prepared.argtypes = [c_void_p, C.c_int32, c_void_p]
         L.sk_align_colmat_words.restype = C.c_int64
         L.sk_align_colmat_words.argtypes = [c_void_p]
         L.sk_align_prepare_cols.argtypes = [c_void_p] * 4
@@ -1088,6 +1099,35 @@ class RealignJob:
         if first < 0:
             raise self._err()
         return first
+
+    def add_reads_prepared(self, reads, prepared):
+        """reads as add_reads takes them (their observed lists are not read), prepared: REALIGN_PREPARED_READ_DTYPE[len(reads)] as realign_preamble
+        leaves them -> first index.  Needs enumeration == 2 and set_indels given the gate's keys in table order; the job then reports only the
+        consulted marks of the search: gate_consulted | preamble_consulted are the caller's to add."""
+        n = len(reads)
+        prepared = np.ascontiguousarray(prepared, REALIGN_PREPARED_READ_DTYPE)
+        assert len(prepared) == n
+        arr = (ReadInput * max(n, 1))()
+        keep = []
+        for i, (read_code, read_qual, pos, path, is_fwd, map_level, sample, realign_range, observed) in enumerate(reads):
+            code = np.ascontiguousarray(read_code, np.uint8)
+            qual = np.ascontiguousarray(read_qual, np.uint8)
+            segs = (PathSeg * max(len(path), 1))(*[PathSeg(t, l) for t, l in path])
+            keep.append((code, qual, segs))
+            arr[i] = ReadInput(_p(code), _p(qual), len(code), pos, len(path), segs, int(is_fwd), map_level, sample, realign_range[0], realign_range[1], 0, None)
+        first = lib().sk_realign_job_add_reads_prepared(self._j, arr, _p(prepared) if n else None, n)
+        if first < 0:
+            raise self._err()
+        return first
+
+    def debug_prepared(self, i):
+        """the record the job's own preamble makes for read i (sk_debug_realign_job_prepared) as a REALIGN_PREPARED_READ_DTYPE scalar, or None when the read
+        has none (it left at the gate, at a capacity or at a negative position)"""
+        out = np.zeros(1, REALIGN_PREPARED_READ_DTYPE)
+        rc = lib().sk_debug_realign_job_prepared(self._j, int(i), _p(out))
+        if rc < 0:
+            raise StrelkaAmdError("sk_debug_realign_job_prepared: bad argument")
+        return None if rc else out[0]
 
     def batch(self):
         s = AlignBatch()
@@ -2222,6 +2262,97 @@ def realign_job_inputs(gate, sample, reads, insert_pool):
         out.append((rd["code"], rd["qual"], rd["pos"], rd["path"], rd.get("fwd", True), rd.get("map_level", MAPLEVEL["TIER1"]), sample, tuple(rd["realign"]),
                     [int(x) for x in so["observed"][b:e]]))
     return indels, out
+
+
+(RPRE_NONE, RPRE_OK, RPRE_NOT_PASSED, RPRE_NEGATIVE_POS, RPRE_EDGE_KEY_MISSING, RPRE_EXEMPLAR_KEY_MISSING, RPRE_CAP_K, RPRE_CAP_OBS, RPRE_CAP_P,
+ RPRE_N_STATUS) = range(10)  # SK_RPRE_*
+RPRE_NAMES = ("NONE", "OK", "NOT_PASSED", "NEGATIVE_POS", "EDGE_KEY_MISSING", "EXEMPLAR_KEY_MISSING", "CAP_K", "CAP_OBS", "CAP_P")
+RPRE_K, RPRE_P, RPRE_OBS, RPRE_N_TOTALS = 40, 48, 64, 1 + RPRE_N_STATUS
+REALIGN_PREPARED_RANGE_DTYPE = np.dtype([("b", "<i4"), ("e", "<i4"), ("has_b", "u1"), ("has_e", "u1"), ("pad", "u1", (2,))])
+REALIGN_PREPARED_ALIGNMENT_DTYPE = np.dtype([("pos", "<i4"), ("lead", "<i2"), ("trail", "<i2"), ("is_fwd_strand", "u1"), ("n_seg", "u1"), ("n_indels", "u1"), ("pad", "u1"),
+                                             ("path", [("type", "<u2"), ("length", "<u2")], (RPRE_P,)), ("indels", "<i2", (RPRE_K + 2,))])
+REALIGN_PREPARED_STATUS_DTYPE = np.dtype([("idx", "<i2"), ("is_present", "u1"), ("is_remove_only", "u1"), ("in_original", "u1"), ("pad", "u1")])
+REALIGN_PREPARED_READ_DTYPE = np.dtype([("realign_begin", "<i4"), ("realign_end", "<i4"), ("read_length", "<i4"), ("sample", "<i4"), ("exemplar_range", REALIGN_PREPARED_RANGE_DTYPE),
+                                        ("alignment", REALIGN_PREPARED_ALIGNMENT_DTYPE), ("status_map", REALIGN_PREPARED_STATUS_DTYPE, (RPRE_K,)), ("order", "<i2", (RPRE_K,)),
+                                        ("observed", "<i2", (RPRE_OBS,)), ("n_status", "u1"), ("n_order", "u1"), ("n_observed", "u1"), ("clipped", "u1"), ("hc_lead", "<u4"),
+                                        ("hc_trail", "<u4"), ("sc_lead", "<u4"), ("sc_trail", "<u4")])
+REALIGN_PREPARED_SOURCE_DTYPE = np.dtype([("sample", "<i4"), ("read", "<i4")])
+assert REALIGN_PREPARED_READ_DTYPE.itemsize == 784 and REALIGN_PREPARED_ALIGNMENT_DTYPE.itemsize == 288 and REALIGN_PREPARED_SOURCE_DTYPE.itemsize == 8
+
+
+class RealignPreambleSample(C.Structure):  # sk_realign_preamble_sample
+    _fields_ = [("read_code", c_void_p), ("read_off", c_void_p), ("code_cap", C.c_int64), ("is_fwd_strand", c_void_p), ("status", c_void_p)]
+
+
+assert C.sizeof(RealignPreambleSample) == 40
+
+
+def pack_preamble_sample(codes, is_fwd=None):
+    """the reads' BAM codes (one array per read) and strands (None: all forward) -> the input arrays of one sk_realign_preamble_sample, each with one
+    element of slack: dict(read_code, read_off, code_cap, is_fwd_strand)"""
+    off = np.zeros(len(codes) + 1, np.int64)
+    for i, c in enumerate(codes):
+        off[i + 1] = off[i] + len(c)
+    flat = np.concatenate([np.asarray(c, np.uint8) for c in codes] + [np.zeros(1, np.uint8)]) if len(codes) else np.zeros(1, np.uint8)
+    return dict(read_code=flat, read_off=off, code_cap=int(off[-1]), is_fwd_strand=None if is_fwd is None else np.array([int(bool(f)) for f in is_fwd] + [0], np.uint8))
+
+
+def realign_preamble(samples, gate, pre, insert_pool, ref, ref_offset, max_indel_size, record_cap=None, n_keys=None, slack=0, host=False):
+    """samples: [pack_gate_sample's dicts]; gate: realign_gate's result (keys, and per sample reads, observed_off, observed); pre: [pack_preamble_sample's
+    dicts]; insert_pool: the table's; ref: the job's reference segment -> dict(records REALIGN_PREPARED_READ_DTYPE[record_cap], source
+    REALIGN_PREPARED_SOURCE_DTYPE[record_cap], status [uint8 per read, per sample], consulted uint8[n_keys], totals [the record count, then the reads per
+    SK_RPRE_* status]) through sk_realign_preamble, or with host=True through sk_debug_realign_preamble_host (the same rules on the host; needs no device).
+    record_cap: None = the reads that passed the gate.  slack: so many extra elements of 0x5a bytes behind every output array, returned with it"""
+    L = lib()
+    n_samples = len(samples)
+    keys = np.ascontiguousarray(gate["keys"], REALIGN_GATE_KEY_DTYPE)
+    nk = len(keys) if n_keys is None else n_keys
+    insert_pool = np.ascontiguousarray(insert_pool, np.uint8)
+    refb = np.frombuffer(ref.encode("latin-1") if isinstance(ref, str) else bytes(ref), np.uint8)
+    if record_cap is None:
+        record_cap = sum(int((np.asarray(g["reads"]["status"][:p["n_reads"]]) == RGATE_PASS).sum()) for g, p in zip(gate["samples"], samples))
+
+    def room(n, dtype):
+        a = np.zeros(max(n, 0) + max(slack, 1), dtype)
+        a.view(np.uint8)[max(n, 0) * a.dtype.itemsize:] = 0x5a
+        return a
+    records, source, consulted = room(record_cap, REALIGN_PREPARED_READ_DTYPE), room(record_cap, REALIGN_PREPARED_SOURCE_DTYPE), room(nk, np.uint8)
+    status = [room(int(p["n_reads"]), np.uint8) for p in samples]
+    totals = np.zeros(RPRE_N_TOTALS, np.int64)
+    keep = []
+
+    def arr(a, dtype):
+        a = np.ascontiguousarray(a, dtype)
+        keep.append(a)
+        return a.ctypes.data
+    arr_in = (RealignGateSample * max(n_samples, 1))(*[realign_gate_sample_struct(dict(p, align_id=None)) for p in samples])
+    arr_gate = (RealignGateSampleOut * max(n_samples, 1))(*[RealignGateSampleOut(arr(g["reads"], REALIGN_GATE_READ_DTYPE), arr(g["observed_off"], np.int64),
+                                                                                 arr(g["observed"], np.int32), int(g.get("observed_cap", len(g["observed"]))))
+                                                             for g in gate["samples"]])
+    arr_pre = (RealignPreambleSample * max(n_samples, 1))(*[RealignPreambleSample(arr(q["read_code"], np.uint8), arr(q["read_off"], np.int64), int(q["code_cap"]),
+                                                                                  None if q["is_fwd_strand"] is None else arr(q["is_fwd_strand"], np.uint8), st.ctypes.data)
+                                                            for q, st in zip(pre, status)])
+    ptr = lambda x: _p(x) if len(x) else None
+    f = L.sk_debug_realign_preamble_host if host else L.sk_realign_preamble
+    _check(f(n_samples, C.addressof(arr_in), C.addressof(arr_gate), C.addressof(arr_pre), ptr(keys), nk, ptr(insert_pool), len(insert_pool), ptr(refb), int(ref_offset), len(refb),
+             int(max_indel_size), _p(records), _p(source), record_cap, _p(consulted), _p(totals)))
+    cut = (lambda a, n: a[:max(n, 0) + slack])
+    return dict(records=cut(records, record_cap), source=cut(source, record_cap), consulted=cut(consulted, nk), totals=[int(x) for x in totals],
+                status=[cut(st, int(p["n_reads"])) for st, p in zip(status, samples)])
+
+
+def realign_preamble_dev(n_samples, samples_addr, gate_addr, pre_addr, dev_keys, dev_table_totals, key_cap, dev_insert_pool, insert_cap, dev_ref, ref_offset, ref_len,
+                         max_indel_size, dev_records, dev_source, record_cap, dev_consulted, dev_totals, dev_scratch, scratch_bytes, stream):
+    """sk_realign_preamble_dev: the three sample arrays are the addresses of host arrays of RealignGateSample / RealignGateSampleOut / RealignPreambleSample whose
+    pointers are device memory, every dev_* an address in device memory; only enqueues on `stream`"""
+    _check(lib().sk_realign_preamble_dev(int(n_samples), samples_addr, gate_addr, pre_addr, dev_keys, dev_table_totals, int(key_cap), dev_insert_pool, int(insert_cap), dev_ref,
+                                         int(ref_offset), int(ref_len), int(max_indel_size), dev_records, dev_source, int(record_cap), dev_consulted, dev_totals, dev_scratch,
+                                         int(scratch_bytes), stream))
+
+
+def realign_preamble_scratch_bytes(n_samples, key_cap, record_cap):
+    """bytes of device scratch sk_realign_preamble_dev needs; host arithmetic, works without a device"""
+    return int(lib().sk_realign_preamble_scratch_bytes(int(n_samples), int(key_cap), int(record_cap)))
 
 
 BAI_CHUNK_DTYPE = np.dtype([("begin", "<u8"), ("end", "<u8")])

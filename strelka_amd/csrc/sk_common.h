@@ -121,7 +121,8 @@ enum {
     SK_DEVERR_INDEL_TABLE = 64u, // sk_indel_table_dev met input its host entry refuses, or a capacity below what the arrays hold
     SK_DEVERR_READ_DEPTH = 128u, // sk_read_depth_dev met an iat above 2 or a path outside path_cap or with a segment type it does not know
     SK_DEVERR_INDEL_CANDIDATES = 256u, // sk_indel_candidates_dev met a rate set, a key count or observations its host entry refuses
-    SK_DEVERR_REALIGN_GATE = 512u // sk_realign_gate_dev met reads, a table or capacities its host entry refuses
+    SK_DEVERR_REALIGN_GATE = 512u, // sk_realign_gate_dev met reads, a table or capacities its host entry refuses
+    SK_DEVERR_REALIGN_PREAMBLE = 1024u // sk_realign_preamble_dev met reads, gate outputs, keys or a record capacity its host entry refuses
 };
 
 SkContext& sk_ctx();

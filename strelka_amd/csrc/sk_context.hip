@@ -402,6 +402,8 @@ int sk_check_device_errors(void)
         return sk_fail("sk_indel_candidates_dev: a rate outside [0,1], a rate set of no or more than 4 sizes or with a count outside 1..40, more keys than key_cap, observations outside obs_cap, or a breakpoint observation without its key");
     if (flags & SK_DEVERR_REALIGN_GATE)
         return sk_fail("sk_realign_gate_dev: a path outside path_cap, a negative segment count or read length, a segment type the path format does not have, align ids not strictly ascending, id sets that do not tile the id pool, an id that belongs to none of its sample's reads, more keys than key_cap, more ids than id_cap, or observed_cap below the ids' count");
+    if (flags & SK_DEVERR_REALIGN_PREAMBLE)
+        return sk_fail("sk_realign_preamble_dev: a path outside path_cap, a negative segment count or read length, a segment type the path format does not have, a gate status outside the enum, a read_off that descends or leaves code_cap, an observed list outside observed_cap, not strictly ascending or with an index outside the table, keys whose positions descend, whose type is none or whose insert lies outside the pool, more keys than key_cap, or record_cap below the reads that pass the gate");
     return sk_fail("strelka_amd: a kernel reported an error");
 }
 

@@ -12,7 +12,7 @@
 // integer containers.  Each function cites the reference lines it reproduces.
 
 #include "strelka_amd.h"
-#include "../csrc/realign_core.h"
+#include "../csrc/preamble_core.h"
 #include "../csrc/read_enumerate.h"
 #include "../csrc/stage3_core.h"
 
@@ -1229,20 +1229,27 @@ bool to_core_read(const Job& job, const std::vector<int>& observed, int sample, 
     return true;
 }
 
-// getCandidateAlignments :1816-1994
-void get_candidate_alignments(const Job& job, sk_realign_job::Read& rd, const std::vector<int>& observed, const Aln& input,
-                              const Range& realign_range, std::set<Cal>& cal_set, const bool force_host = false)
+// what getCandidateAlignments holds when it calls candidate_alignment_search (:1816-1957)
+struct Preamble
 {
-    const unsigned read_length = unsigned(rd.code.size());
+    Cal cal; // the normalised input alignment with its edge indels, clipped
     StatusMap sm;
-    HapMap hm;
     std::vector<int> order;
-
-    Cal cal;
+    Range exemplar_pr; // from before the clip
+    unsigned cal_read_length = 0, hc_lead = 0, hc_trail = 0, sc_lead = 0, sc_trail = 0;
+    bool clipped = false;
+};
+void host_preamble(const SearchCtx& ctx, const std::vector<uint8_t>& code, const Aln& input, Preamble& p)
+{
+    const Job& job = ctx.job;
+    const unsigned read_length = unsigned(code.size());
+    StatusMap& sm = p.sm;
+    std::vector<int>& order = p.order;
+    Cal& cal = p.cal;
     cal.al = input;
     bool has_lead, has_trail;
     Key lead_k, trail_k;
-    input_edge_keys(input, rd.code, has_lead, lead_k, has_trail, trail_k);
+    input_edge_keys(input, code, has_lead, lead_k, has_trail, trail_k);
     if (has_lead) {
         cal.lead = job.find_key(lead_k);
         if (cal.lead < 0) throw Fail("leading edge indel of the input alignment is not in the indel table");
@@ -1252,12 +1259,11 @@ void get_candidate_alignments(const Job& job, sk_realign_job::Read& rd, const st
         if (cal.trail < 0) throw Fail("trailing edge indel of the input alignment is not in the indel table");
     }
 
-    SearchCtx ctx{ job, observed, rd.sample, read_length, realign_range, cal_set, rd.warn_origin, rd.warn_toggle };
-    const Range exemplar_pr = soft_clip_range(cal.al);
+    const Range exemplar_pr = p.exemplar_pr = soft_clip_range(cal.al);
     add_indels_in_range(ctx, exemplar_pr, sm, order);
     {
         std::set<Key> keys;
-        alignment_indel_keys(job, cal.al, has_lead ? &lead_k : nullptr, has_trail ? &trail_k : nullptr, rd.code, true, keys);
+        alignment_indel_keys(job, cal.al, has_lead ? &lead_k : nullptr, has_trail ? &trail_k : nullptr, code, true, keys);
         ISet valid;
         bool recompute = false;
         for (const Key& k : keys) {
@@ -1281,22 +1287,44 @@ void get_candidate_alignments(const Job& job, sk_realign_job::Read& rd, const st
     for (const auto& kv : sm) if (!kv.second.is_present) order.push_back(kv.first);
     sort_remove_only_indels_last(sm, order);
 
-    unsigned cal_read_length = read_length, hc_lead = 0, hc_trail = 0, sc_lead = 0, sc_trail = 0;
-    const bool clipped = path_is_clipped(cal.al.path);
-    if (clipped) {
-        clip_clipper(cal.al.path, hc_lead, hc_trail, sc_lead, sc_trail);
-        cal_read_length -= (sc_lead + sc_trail);
+    p.cal_read_length = read_length;
+    p.clipped = path_is_clipped(cal.al.path);
+    if (p.clipped) {
+        clip_clipper(cal.al.path, p.hc_lead, p.hc_trail, p.sc_lead, p.sc_trail);
+        p.cal_read_length -= (p.sc_lead + p.sc_trail);
     }
+}
+// the preamble's state in the core's form, clip counts included; false = beyond a cap
+bool preamble_record(const Job& job, const std::vector<int>& observed, int sample, const Range& realign_range, const Preamble& p, skcore::PRead& r)
+{
+    if (!to_core_read(job, observed, sample, p.cal_read_length, realign_range, p.exemplar_pr, p.sm, p.order, p.cal, r)) return false;
+    r.clipped = p.clipped ? 1 : 0;
+    r.hc_lead = p.hc_lead;
+    r.hc_trail = p.hc_trail;
+    r.sc_lead = p.sc_lead;
+    r.sc_trail = p.sc_trail;
+    return true;
+}
+
+// getCandidateAlignments :1816-1994
+void get_candidate_alignments(const Job& job, sk_realign_job::Read& rd, const std::vector<int>& observed, const Aln& input,
+                              const Range& realign_range, std::set<Cal>& cal_set, const bool force_host = false)
+{
+    HapMap hm;
+    SearchCtx ctx{ job, observed, rd.sample, unsigned(rd.code.size()), realign_range, cal_set, rd.warn_origin, rd.warn_toggle };
+    Preamble p;
+    host_preamble(ctx, rd.code, input, p);
+    const StatusMap& sm = p.sm;
+    const std::vector<int>& order = p.order;
+    const Cal& cal = p.cal;
+    const Range exemplar_pr = p.exemplar_pr;
+    const unsigned cal_read_length = p.cal_read_length, hc_lead = p.hc_lead, hc_trail = p.hc_trail, sc_lead = p.sc_lead, sc_trail = p.sc_trail;
+    const bool clipped = p.clipped;
     ctx.read_length = cal_read_length;
     bool searched = false;
     if (job.opt.enumeration == 2 && !force_host) {
         std::shared_ptr<skcore::PRead> pr(new skcore::PRead);
-        if (to_core_read(job, observed, rd.sample, cal_read_length, realign_range, exemplar_pr, sm, order, cal, *pr)) {
-            pr->clipped = clipped ? 1 : 0;
-            pr->hc_lead = hc_lead;
-            pr->hc_trail = hc_trail;
-            pr->sc_lead = sc_lead;
-            pr->sc_trail = sc_trail;
+        if (preamble_record(job, observed, rd.sample, realign_range, p, *pr)) {
             rd.pending = pr;
             return;
         }
@@ -2036,6 +2064,15 @@ bool passes_gate(const Job& job, const Aln& input, const unsigned read_len, cons
     return false;
 }
 
+// normalizeInputAlignmentIndels :2001-2021 (no pinned edges on DNA reads)
+Aln normalised_input(const Aln& input)
+{
+    Aln norm = input;
+    if (is_edge_readref_len_segment(norm.path)) norm = matchify_edge_indels(norm, true, true);
+    if (path_is_soft_clipped(norm.path)) norm = matchify_edge_segment_type(norm, SK_SEG_SOFT_CLIP); // :2051-2057
+    return norm;
+}
+
 void enumerate_read(const Job& job, sk_realign_job::Read& rd, const bool force_host)
 {
     const Range realign_range(rd.realign_b, rd.realign_e);
@@ -2046,10 +2083,7 @@ void enumerate_read(const Job& job, sk_realign_job::Read& rd, const bool force_h
     std::set<Cal> cal_set;
     const bool gate = passes_gate(job, rd.input, read_len, realign_range);
     if (gate) {
-        // normalizeInputAlignmentIndels :2001-2021 (no pinned edges on DNA reads)
-        Aln norm = rd.input;
-        if (is_edge_readref_len_segment(norm.path)) norm = matchify_edge_indels(norm, true, true);
-        if (path_is_soft_clipped(norm.path)) norm = matchify_edge_segment_type(norm, SK_SEG_SOFT_CLIP); // :2051-2057
+        const Aln norm = normalised_input(rd.input);
         if (norm.pos >= 0) {
             get_candidate_alignments(job, rd, rd.observed, norm, realign_range, cal_set, force_host);
             if (cal_set.empty() && !rd.pending) throw Fail("Empty candidate alignment set while realigning normed input alignment");
@@ -2059,9 +2093,8 @@ void enumerate_read(const Job& job, sk_realign_job::Read& rd, const bool force_h
     rd.cals.assign(cal_set.begin(), cal_set.end());
 }
 
-// stage 1 for one read: validation, gate, normalisation, enumeration.  Touches nothing but `rd` (the job is read-only here),
-// so reads can be prepared concurrently.  Throws Fail.
-void prepare_read(const Job& job, const sk_read_input* in, sk_realign_job::Read& rd)
+// what is checked of a read before anything is done with it, and the read's plain fields.  Throws Fail.
+void read_from_input(const Job& job, const sk_read_input* in, sk_realign_job::Read& rd)
 {
     if (in->read_len < 0 || in->n_seg < 0 || in->n_observed < 0) throw Fail("negative read, path or observed-list length");
     if ((in->read_len > 0 && (in->read_code == nullptr || in->read_qual == nullptr)) || (in->n_seg > 0 && in->path == nullptr) ||
@@ -2087,6 +2120,21 @@ void prepare_read(const Job& job, const sk_read_input* in, sk_realign_job::Read&
         if (in->observed[i] < 0 || size_t(in->observed[i]) >= job.orig_to_tab.size()) throw Fail("observed indel index out of range");
     rd.realign_b = in->realign_begin;
     rd.realign_e = in->realign_end;
+}
+// the device scores pending reads without passing the builder, whose check this is
+void check_qualities(const std::vector<uint8_t>& qual)
+{
+    for (const uint8_t q : qual)
+        if (q > 70) // qphred_cache::high_qscore_error, L/blt_util/qscore_cache.cpp:66-75
+            throw Fail("flatten: Attempting to lookup basecall quality score " + std::to_string(int(q)) +
+                       " which exceeds the maximum cached basecall quality score of 70");
+}
+
+// stage 1 for one read: validation, gate, normalisation, enumeration.  Touches nothing but `rd` (the job is read-only here),
+// so reads can be prepared concurrently.  Throws Fail.
+void prepare_read(const Job& job, const sk_read_input* in, sk_realign_job::Read& rd)
+{
+    read_from_input(job, in, rd);
     // a read that does not pass the gate (most reads of a sample, away from candidate indels) is done: its bases, qualities and
     // observed indels are never looked at
     if (!passes_gate(job, rd.input, rd.read_len, Range(rd.realign_b, rd.realign_e))) {
@@ -2102,11 +2150,44 @@ void prepare_read(const Job& job, const sk_read_input* in, sk_realign_job::Read&
     std::sort(rd.observed.begin(), rd.observed.end());
     rd.observed.erase(std::unique(rd.observed.begin(), rd.observed.end()), rd.observed.end());
     enumerate_read(job, rd, false);
-    if (rd.pending) // the device scores these reads without passing the builder, whose check this is
-        for (const uint8_t q : rd.qual)
-            if (q > 70) // qphred_cache::high_qscore_error, L/blt_util/qscore_cache.cpp:66-75
-                throw Fail("flatten: Attempting to lookup basecall quality score " + std::to_string(int(q)) +
-                           " which exceeds the maximum cached basecall quality score of 70");
+    if (rd.pending) check_qualities(rd.qual);
+}
+
+// a read whose gate and preamble ran elsewhere: validated as prepare_read validates it, its record checked against the table and the
+// core's capacities (the search indexes with what the record holds), and left pending.  Throws Fail.
+void prepare_given_read(const Job& job, const sk_read_input* in, const sk_realign_prepared_read& given, sk_realign_job::Read& rd)
+{
+    read_from_input(job, in, rd);
+    skcore::PRead pr;
+    static_assert(sizeof(pr) == sizeof(given), "sk_realign_prepared_read is skcore::PRead");
+    std::memcpy(&pr, &given, sizeof(pr));
+    const int n_tab = int(job.tab.size());
+    const auto in_tab = [&](const int i) { return i >= 0 && i < n_tab; };
+    if (pr.n_sm > skcore::Caps::K || pr.n_order > skcore::Caps::K || pr.n_observed > skcore::Caps::OBS || pr.cal.n_seg > skcore::Caps::P || pr.cal.n_indels != 0)
+        throw Fail("prepared record: a count above the core's capacities (status map and order 40, observed 64, path 48)");
+    if (pr.sample != in->sample_index) throw Fail("prepared record: its sample is not the read's sample_index");
+    if (pr.read_length < 0 || pr.read_length > 0xffff || pr.read_length > in->read_len) throw Fail("prepared record: read_length outside the read");
+    if ((pr.cal.lead != -1 && !in_tab(pr.cal.lead)) || (pr.cal.trail != -1 && !in_tab(pr.cal.trail))) throw Fail("prepared record: an edge indel index outside the indel table");
+    for (int i = 0; i < pr.cal.n_seg; ++i)
+        if (pr.cal.path[i].type > SK_SEG_SEQ_MISMATCH || pr.cal.path[i].type == SK_SEG_SKIP) throw Fail("prepared record: a path segment type the search does not take");
+    for (int i = 0; i < pr.n_sm; ++i) {
+        if (!in_tab(pr.sm[i].idx)) throw Fail("prepared record: a status map index outside the indel table");
+        if (i > 0 && !(pr.sm[i - 1].idx < pr.sm[i].idx)) throw Fail("prepared record: the status map is not strictly ascending");
+    }
+    if (pr.n_order != pr.n_sm) throw Fail("prepared record: the order is not as long as the status map");
+    for (int i = 0; i < pr.n_order; ++i) {
+        if (skcore::sm_find(pr, pr.order[i]) < 0) throw Fail("prepared record: an order entry that is not in the status map");
+        for (int q = 0; q < i; ++q)
+            if (pr.order[q] == pr.order[i]) throw Fail("prepared record: an order entry twice");
+    }
+    for (int i = 0; i < pr.n_observed; ++i)
+        if (!in_tab(pr.observed[i]) || (i > 0 && !(pr.observed[i - 1] < pr.observed[i]))) throw Fail("prepared record: the observed list is not strictly ascending inside the indel table");
+    rd.code.assign(in->read_code, in->read_code + in->read_len);
+    rd.qual.assign(in->read_qual, in->read_qual + in->read_len);
+    check_qualities(rd.qual);
+    rd.observed.assign(pr.observed, pr.observed + pr.n_observed); // (what a host search needs should the device turn the read down)
+    rd.warn_origin = rd.warn_toggle = rd.incomplete_search = false;
+    rd.pending = std::make_shared<skcore::PRead>(pr);
 }
 
 // flatten a prepared read's candidate alignments into `builder`; returns the number of candidate alignments added
@@ -2252,6 +2333,66 @@ int sk_realign_job_add_reads(sk_realign_job* j, const sk_read_input* in, int32_t
         return first;
     } catch (const std::exception& e) {
         j->error = e.what();
+        return -1;
+    }
+}
+
+int sk_realign_job_add_reads_prepared(sk_realign_job* j, const sk_read_input* in, const sk_realign_prepared_read* prepared, int32_t n)
+{
+    if (!j || ((!in || !prepared) && n > 0) || n < 0) return -1;
+    try {
+        if (j->finished) throw Fail("job already finished: clear the reads first");
+        if (j->opt.enumeration != 2) throw Fail("sk_realign_job_add_reads_prepared: prepared reads start the device search, which needs enumeration == 2");
+        if (j->tab.size() > size_t(skcore::PRE_MAX_TAB)) throw Fail("sk_realign_job_add_reads_prepared: a prepared record cannot index a table above 32000 indels");
+        for (size_t i = 0; i < j->orig_to_tab.size(); ++i)
+            if (j->orig_to_tab[i] != int(i)) throw Fail("sk_realign_job_add_reads_prepared: the indel table was not given in key order, which is what the records index");
+        std::vector<sk_realign_job::Read> fresh(static_cast<size_t>(n));
+        for (int32_t i = 0; i < n; ++i) {
+            try {
+                prepare_given_read(*j, in + i, prepared[i], fresh[size_t(i)]);
+            } catch (const std::exception& ex) {
+                throw Fail("read " + std::to_string(i) + ": " + ex.what());
+            }
+        }
+        const int first = int(j->reads.size());
+        for (auto& rd : fresh) {
+            rd.cal_begin = j->n_cals_total; // (the batch is assembled by the job's run)
+            j->reads.push_back(std::move(rd));
+        }
+        return first;
+    } catch (const std::exception& e) {
+        j->error = e.what();
+        return -1;
+    }
+}
+
+int sk_debug_realign_job_prepared(const sk_realign_job* j, int32_t read_index, sk_realign_prepared_read* out)
+{
+    if (!j || !out || read_index < 0 || size_t(read_index) >= j->reads.size()) return -1;
+    const sk_realign_job::Read& rd = j->reads[size_t(read_index)];
+    try {
+        const Range realign_range(rd.realign_b, rd.realign_e);
+        // (the questions adding the read asked, asked again: the marks stay as they are)
+        if (!passes_gate(*j, rd.input, rd.read_len, realign_range)) return 1;
+        const Aln norm = normalised_input(rd.input);
+        if (norm.pos < 0) return 1;
+        std::set<Cal> cal_set;
+        bool warn_origin = false, warn_toggle = false;
+        const SearchCtx ctx{ *j, rd.observed, rd.sample, unsigned(rd.code.size()), realign_range, cal_set, warn_origin, warn_toggle };
+        Preamble p;
+        host_preamble(ctx, rd.code, norm, p);
+        skcore::PRead r;
+        if (!preamble_record(*j, rd.observed, rd.sample, realign_range, p, r)) return 1;
+        std::memset(out, 0, sizeof(*out));
+        const skcore::PRange er = r.exemplar_range;
+        std::memset(&r.exemplar_range, 0, sizeof(r.exemplar_range)); // (a range assigned as a whole brings its padding along)
+        r.exemplar_range.b = er.b;
+        r.exemplar_range.e = er.e;
+        r.exemplar_range.has_b = er.has_b;
+        r.exemplar_range.has_e = er.has_e;
+        std::memcpy(out, &r, sizeof(r));
+        return 0;
+    } catch (const std::exception&) {
         return -1;
     }
 }
